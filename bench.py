@@ -120,6 +120,61 @@ def make_stream_frames(seed, count, workers):
     return synth.make_frames_parallel(seed, W, H, count, workers)
 
 
+DUMP_FRAMES, DUMP_SEED, DUMP_LIMIT = 64, 20240613, 64 << 20
+
+
+def snapshot_outputs(ctxs, use_bow, match):
+    """Host copies of what one step left in the contexts' device buffers, joined over the contexts in batch order."""
+    from orbhip.capi import KP_DTYPE
+    names = ["cnt", "kps", "desc"] + (["word", "wt", "node", "m12", "m21", "nm"] if use_bow else []) + \
+        (["bi", "bd", "sd"] if match in ("brute", "both") else [])
+    out = {n: np.concatenate([b[n].cpu().numpy() for _, b in ctxs]) for n in names}
+    out["kps"] = np.ascontiguousarray(out["kps"]).view(KP_DTYPE).reshape(out["kps"].shape[:2])
+    return out
+
+
+def dump_outputs(path, snap):
+    """--dump-outputs: the step's results for a fixed, seeded sample of the batch's frames, as DIR/<name>.npy (float64, or float32
+    where the result is 32-bit float or a descriptor byte), rows of the sampled frames concatenated in frame order.
+      counts (B,)                   keypoints per frame, every frame
+      sample_frames (S,)            the sampled frames
+      keypoints (N, 7)              x, y, size, angle, response, octave, class_id of each sampled frame's keypoints
+      descriptors (N, 32)           their descriptor bytes
+    --match bow / both, the vocabulary transform of those keypoints and SearchByBoW of frame b against frame b - 1 (frame 0 has no
+    pair and is left out of the sample when B > 1):
+      word_id, weight, node_id (N,) ; match12 (M,) over frame b - 1's keypoints ; match21 (N,) ; nmatches (S,)
+    --match brute / both, best / second Hamming distance of frame b's keypoints against frame b - 1's:
+      best_idx, best_dist, second_dist (N,)"""
+    cnt = snap["cnt"].astype(np.int64)
+    B = len(cnt)
+    first = 1 if B > 1 else 0
+    S = min(DUMP_FRAMES, B - first)
+    frames = np.sort(np.random.default_rng(DUMP_SEED).choice(np.arange(first, B), S, replace=False))
+
+    def rows(name, lag=0):
+        return np.concatenate([snap[name][b, :cnt[b - lag]] for b in frames])
+    kps = rows("kps")
+    res = {"counts": cnt.astype(np.float64), "sample_frames": frames.astype(np.float64),
+           "keypoints": np.stack([kps[f].astype(np.float64) for f in kps.dtype.names], axis=1),
+           "descriptors": rows("desc").astype(np.float32)}
+    if "m12" in snap and first:
+        res.update(word_id=rows("word").astype(np.float64), weight=rows("wt").astype(np.float32),
+                   node_id=rows("node").astype(np.float64), match12=rows("m12", lag=1).astype(np.float64),
+                   match21=rows("m21").astype(np.float64), nmatches=snap["nm"][frames].astype(np.float64))
+    elif "word" in snap:
+        res.update(word_id=rows("word").astype(np.float64), weight=rows("wt").astype(np.float32),
+                   node_id=rows("node").astype(np.float64))
+    if "bi" in snap:
+        res.update(best_idx=rows("bi").astype(np.float64), best_dist=rows("bd").astype(np.float64),
+                   second_dist=rows("sd").astype(np.float64))
+    total = sum(a.nbytes for a in res.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def oracle_worker(path, first, last, match, out_path):
     """Child process of oracle_outputs_parallel: frames [first, last) of the batch through the oracle (frame first - 1 too, for the
     pair), results to an .npz.  Never touches the GPU."""
@@ -880,7 +935,11 @@ def main():
                     "(the headline stays at --batch: the profiles and every per-launch figure refer to it)")
     ap.add_argument("--streams-config", type=int, default=-1, help="N > 1: also run BASELINE config 4 proper, one EuRoC stream per "
                     "rank (-1 = when N >= 4; 1 = always; 0 = never)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a fixed, seeded "
+                    "sample of the batch's frames) to DIR/<name>.npy; see dump_outputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_tiling is not None:
         args.tiled_check = args.no_tiling
     if args.cpu_worker:
@@ -1057,6 +1116,8 @@ def main():
             stage[1] += ms[1]
     barrier()
     dt = time.perf_counter() - t0
+    # what the last timed step computed, copied out before anything below runs the step again
+    last_step = snapshot_outputs(ctxs, use_bow, args.match) if (args.dump_outputs and rank == 0) else None
     for ex, _ in ctxs:
         assert L.orbhip_set_stage_timing(ex.handle, 2) == 0
     stage_pass = max(1, min(5, args.steps))
@@ -1301,6 +1362,8 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+    if last_step is not None:
+        dump_outputs(args.dump_outputs, last_step)
     if rank == 0:
         # the JSON line is the LAST thing on stdout (RCCL prints its own banner lines earlier)
         C.CDLL(None).fflush(None)      # libc-buffered banner text of RCCL / the HIP runtime goes out first

@@ -447,19 +447,14 @@ int orbhip_remap_device(orbhip_ctx *ctx, const void *d_src, int B, int src_w, in
 
 /* Device time of the stages of the last extract call on this context, in ms:
  * {pyramid, FAST, quadtree, blur, describe} and, at [5], of the last orbhip_hamming_knn2*_device
- * call.  Measured with HIP events on the context's stream; synchronises the stream. */
+ * call.  Measured with HIP events on the context's stream; synchronises the stream.  A batch of 16 frames or more runs
+ * the quadtree in two halves, the second on another stream: [2] is the first half only.  [3] is 0 when the blur ran
+ * inside the describe kernel (the default for batches). */
 int orbhip_get_stage_times(orbhip_ctx *ctx, float ms[6]);
 /* Which of those events the extract / match calls record: 2 (default) all of them, 1 only the pair around the FAST launch
  * (the other entries read 0), 0 none.  An event between two kernels of a stream costs a few microseconds of device time;
  * a loop that only wants its throughput (and bench.py, which wants the FAST launch time) narrows the set. */
 int orbhip_set_stage_timing(orbhip_ctx *ctx, int mode);
-/* Scheduling of the batched path (affects speed only, never a result): where the Gaussian blur (ref:
- * src/ORBextractor.cc:1103-1104) runs.  0 (default): on the context's second stream behind FAST -- FAST, the kernel whose
- * roofline is reported, owns the device while it runs; the quadtree is cut into two half-batches, the first beside the blur,
- * the second beside the describe kernel of the first half; 1: one launch from the end of the pyramid, beside FAST and the
- * quadtree; 2: alone on the main stream between FAST and the quadtree (every kernel owns the device: per-kernel counters).
- * Also ORBHIP_BLUR_PLACE at context creation. */
-int orbhip_set_blur_placement(orbhip_ctx *ctx, int place);
 
 /* ---- resident feature sets (new) ----
  * A key frame's descriptors, keypoints, FeatureVector and feature grid never change after KeyFrame::KeyFrame / ComputeBoW

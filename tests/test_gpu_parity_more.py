@@ -185,10 +185,8 @@ def test_alternative_code_paths_give_the_same_results(env):
     {"ORBHIP_FAST_LISTCAP": "24", "ORBHIP_FAST_FIX": "0"},
     {"ORBHIP_DESCRIBE_AX4": "0"},             # angle phase of the batch describe kernel: five dword loads + masks instead of one dwordx4 load + constant weights
     {"ORBHIP_DESCRIBE_KPW": "32"},            # ... 32 slots per workgroup (always the dword form)
-    {"ORBHIP_NO_SPLIT": "1"},                 # batch schedules: no half-batch split; blur beside FAST
-    {"ORBHIP_BLUR_PLACE": "1"},
-    {"ORBHIP_RESIZE_FIT": "0"},               # k_resize<32> (128 x 32 tiles), what a level keeps when no fitted geometry passes the window check
-    {"ORBHIP_FUSE_BLUR": "1"},                # levels 1.. and their blurred twins from one kernel per level (k_resize_blur)
+    pytest.param({"ORBHIP_RESIZE_FIT": "0"}, id="env10"),   # k_resize<32> (128 x 32 tiles), what a level keeps when no fitted geometry
+                                                            # passes the window check (the id it had when the list held three more cases)
 ])
 def test_alternative_batch_code_paths_give_the_same_results(env):
     """The switchable choices of the BATCH path (read once per process): 16-frame batches of two geometries -- one inside the

@@ -176,3 +176,39 @@ def test_stage_timing_modes_change_no_result():
         assert got == want, mode
     assert L.orbhip_set_stage_timing(ex.handle, 3) != 0
     ex.close()
+
+
+@pytest.mark.gpu
+def test_blur_stage_time_only_after_a_blur_launch():
+    """The blur entry of orbhip_get_stage_times reads the blur launch's own events: after a batch through k_describe_blur it is 0,
+    also once orbhip_debug_get_blurred_level has built the blurred pyramid on request (that launch records no stage events); after
+    a batch through k_blur + k_describe (ORBHIP_DESCRIBE_FUSED=0, ablation library) it is the blur's time."""
+    import os
+    import subprocess
+    import sys
+    code = (
+        "import sys, ctypes as C\n"
+        "sys.path[:0] = [%r]\n"
+        "from orbhip import synth\n"
+        "from orbhip.extractor import ORBextractor\n"
+        "W, H, B = 400, 300, 16\n"
+        "ex = ORBextractor(600, 1.2, 6, 20, 7, max_w=W, max_h=H, max_batch=B)\n"
+        "L = ex._L\n"
+        "assert L.orbhip_set_stage_timing(ex.handle, 2) == 0\n"
+        "ex.extract_batch(synth.make_frames(5, W, H, B))\n"
+        "if sys.argv[1] == 'fused':\n"
+        "    ex.blurred(2, 3)\n"
+        "ms = (C.c_float * 6)()\n"
+        "assert L.orbhip_get_stage_times(ex.handle, ms) == 0\n"
+        "print('blur_ms', ms[3], 'describe_ms', ms[4])\n"
+        "ex.close()\n"
+    ) % os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "vi-orb-slam-icra2018_amd")
+    env = {k: v for k, v in os.environ.items() if not k.startswith("ORBHIP_")}
+    times = {}
+    for path, extra in (("fused", {}), ("two_kernel", {"ORBHIP_DESCRIBE_FUSED": "0"})):
+        out = subprocess.run([sys.executable, "-c", code, path], env=dict(env, **extra), capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0 and "blur_ms" in out.stdout, out.stdout + out.stderr
+        f = out.stdout.split()
+        times[path] = (float(f[f.index("blur_ms") + 1]), float(f[f.index("describe_ms") + 1]))
+    assert times["fused"][0] == 0 and times["fused"][1] > 0, times
+    assert times["two_kernel"][0] > 0 and times["two_kernel"][1] > 0, times

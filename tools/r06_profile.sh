@@ -43,12 +43,12 @@ bash tools/fast_ablate.sh > $OUT/fast_ablate_time.txt 2>&1
 bash tools/fast_ablate_content.sh > $OUT/fast_ablate_content.txt 2>&1      # the same stops per content class (photographs: score + suppression)
 bash tools/bow_ablate.sh > $OUT/bow_ablate_time.txt 2>&1                   # k_bow_lane / k_bow_seq by phase
 # k_describe_blur by phase (stops: 0 slot decode; 1 + disc loads and moments; 2 + angles; 3 + staging and blur; 4 everything; 5 = everything
-# but the disc loads), the kernel alone on the device (quadtree in front of it) and in the default schedule; then by occupancy
-for sc in 0 1; do for p in 0 1 2 3 4 5; do
-  ORBHIP_DESCRIBE_FUSED_SCHED=$sc ORBHIP_DESCRIBE_PHASES=$p python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('schedule $sc stop<=$p describe_ms', d['stage_ms']['describe'], 'quadtree_ms', d['stage_ms']['quadtree'], 'frames/s', d['value'])"
-done; done > $OUT/describe_blur_ablate.txt 2>&1
+# but the disc loads) in the default schedule; then by occupancy
+for p in 0 1 2 3 4 5; do
+  ORBHIP_DESCRIBE_PHASES=$p python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stop<=$p describe_ms', d['stage_ms']['describe'], 'quadtree_ms', d['stage_ms']['quadtree'], 'frames/s', d['value'])"
+done > $OUT/describe_blur_ablate.txt 2>&1
 for pad in 0 8192 16384 28000; do
-  ORBHIP_DESCRIBE_FUSED_SCHED=0 ORBHIP_DESCRIBE_PADLDS=$pad python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('unused LDS $pad describe_ms (alone)', d['stage_ms']['describe'])"
+  ORBHIP_DESCRIBE_PADLDS=$pad python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('unused LDS $pad describe_ms', d['stage_ms']['describe'])"
 done >> $OUT/describe_blur_ablate.txt 2>&1
 # the two-kernel path of rounds 1-5 (k_blur + k_describe) in the same call, for the comparison
 ORBHIP_DESCRIBE_FUSED=0 python bench.py --cpu-frames 0 --pipelined 0 --verify -1 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('k_blur + k_describe (ORBHIP_DESCRIBE_FUSED=0):', d['value'], 'frames/s', d['stage_ms'], 'verified', d['verified_frames'])" >> $OUT/describe_blur_ablate.txt 2>&1

@@ -48,7 +48,6 @@ int orb_configure(orbhip_ctx *c, int w, int h, int stride0, int B)
         // resize tables
         std::vector<int32_t> all;
         bool chainOk[ORBHIP_MAX_LEVELS] = {};
-        c->fuseBlurOk = c->nlevels > 1;
         for (int l = 1; l < c->nlevels; l++) {
             std::vector<int32_t> xt, yt;
             orb_build_resize_tables(c->G.lv[l - 1].w, c->G.lv[l - 1].h, c->G.lv[l].w, c->G.lv[l].h, xt, yt);
@@ -65,8 +64,6 @@ int orb_configure(orbhip_ctx *c, int w, int h, int stride0, int B)
             c->resizeFit[l] = ResizeFit();
             if (c->resizeGroups[l] && !resize_fit_plan(xt.data(), yt.data(), c->G.lv[l - 1].w, c->G.lv[l - 1].h, c->G.lv[l].w, c->G.lv[l].h, c->resizeFit[l]))
                 c->resizeFit[l] = ResizeFit();
-            c->fuseBlurOk = c->fuseBlurOk && c->resizeGroups[l] &&
-                            resize_blur_fits(xt.data(), yt.data(), c->G.lv[l - 1].w, c->G.lv[l - 1].h, c->G.lv[l].w, c->G.lv[l].h);
             while (all.size() % 4) all.push_back(0);
             c->resizeTabOff[l][2] = all.size();
             if (c->resizeGroups[l]) all.insert(all.end(), gt.begin(), gt.end());
@@ -144,7 +141,6 @@ extern "C" orbhip_ctx *orbhip_create(int device, int nfeatures, float scaleFacto
     }
     orbhip_ctx *c = new orbhip_ctx();
     c->device = device;
-    c->blurPlace = std::min(2, std::max(0, ORB_TUNE("BLUR_PLACE", 0)));
     c->max_w = max_w;
     c->max_h = max_h;
     c->max_batch = max_batch;
@@ -315,21 +311,12 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
             launch_pyramid_chain(s, G, c->chainLevels, grp, c->d_chainTiles, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes,
                                  c->d_resizeTab, B, h_pyr_dst);   // (the host copy of the pyramid is written by the kernel itself)
     // batches: level l from level l-1 (sequential dependency), all frames per launch
-    // ORBHIP_FUSE_BLUR=1 (r05 experiment): levels 1.. and their blurred twins from one kernel per level; k_blur keeps level 0
-    static const bool fuseSwitch = ORB_TUNE("FUSE_BLUR", 0) != 0;   // (liborbhip_ablation.so only: measured slower)
-    const bool fuseBlur = fuseSwitch && B >= 8 && !chained && c->fuseBlurOk;
     static const bool fitTiles = ORB_TUNE("RESIZE_FIT", 1) != 0;   // batches: tiles fitted to the level (k_resize_fit)
     for (int l = 1; l < G.nlevels && !chained; l++) {
         const OrbLevel &S = G.lv[l - 1], &D = G.lv[l];
         const uint8_t *src = (l == 1) ? lvl0 : c->d_pyr + S.imgOff;
         const int sstride = (l == 1) ? stride0 : S.stride;
         const size_t sframe = (l == 1) ? frame0 : c->pyrFrameBytes;
-        if (fuseBlur) {
-            launch_resize_blur(s, src, S.w, S.h, sstride, sframe, c->d_pyr + D.imgOff, D.w, D.h, D.stride, c->pyrFrameBytes,
-                               c->d_blur + G.boff1 + D.imgOff, D.stride, c->lvl0FrameBytes + c->pyrFrameBytes,
-                               c->d_resizeTab + c->resizeTabOff[l][1], c->d_resizeTab + c->resizeTabOff[l][2], c->d_blurBands, B);
-            continue;
-        }
         if (fitTiles && B >= 8 && c->resizeFit[l].ntx > 0) {
             launch_resize_fit(s, src, S.w, S.h, sstride, sframe, c->d_pyr + D.imgOff, D.w, D.h, D.stride, c->pyrFrameBytes,
                               c->d_resizeTab + c->resizeTabOff[l][1], c->d_resizeTab + c->resizeTabOff[l][2], c->resizeFit[l], B);
@@ -343,7 +330,8 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     if (evFast) HIPCHK(c, hipEventRecord(c->ev[1], s));
     // host copy of levels 1.. (orbhip_set_host_pyramid): one copy of the B frames' pyramid block into pinned memory.  A
     // frame or two: on the second stream, beside FAST / quadtree / blur / describe (those do not use it then); the main
-    // stream joins it at the end.  Batches (the second stream carries the blur): behind the describe kernel.
+    // stream joins it at the end.  Batches (the second stream carries quadtree(B), and the blur of the two-kernel schedule):
+    // behind the describe kernel.
     const bool pyrFork = h_pyr_dst && B < 8 && G.nlevels > 1 && !chained;
     if (pyrFork) {
         HIPCHK(c, hipEventRecord(c->evp[0], s));
@@ -352,25 +340,23 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
         HIPCHK(c, hipEventRecord(c->evp[1], c->stream2));
     }
     // E3 FAST, E4 quadtree, E6 blur, E5 + E7 describe.  FAST runs ALONE on the device (it is the kernel whose roofline is
-    // reported).  Batches, default schedule (blur placement 0): the quadtree is a latency-bound kernel of few long workgroups,
-    // so it is cut in two half-batches that hide behind kernels which do not depend on them -- the first half beside the blur
-    // (second stream), the second half beside the describe kernel of the FIRST half:
-    //     main stream  : FAST(all) | quadtree(A) | describe(A)            | describe(B)
-    //     second stream:           | blur(all)   | quadtree(B)            |
-    // Other placements of the blur (orbhip_set_blur_placement): 1 = one launch from the end of the pyramid, beside FAST and
-    // the quadtree; 2 = alone on the main stream between FAST and the quadtree (every kernel owns the device: counters).
-    // A frame or two: one cell per FAST workgroup (four times the workgroups, each a shorter chain -- the single-frame FAST
-    // time is one workgroup's latency), everything on one stream (a cross-stream hand-over costs more than it hides).
-    const int blurPlace = c->blurPlace;
-    const size_t blurFrame = c->lvl0FrameBytes + c->pyrFrameBytes;
-    // r06, batches: the blur inside the describe kernel (k_describe_blur) -- no blurred pyramid, no k_blur.  Schedule:
+    // reported).  Batches: the quadtree is a latency-bound kernel of few long workgroups, so from 16 frames up it is cut into
+    // two halves, A = [0, B/2) and B = [B/2, B), that hide behind kernels which do not depend on them.  Two schedules:
+    //   fused describe (k_describe_blur: the blur inside the describe kernel, no blurred pyramid; describe_blur_available):
     //     main stream  : FAST(all) | quadtree(A) | describe+blur(A)       | describe+blur(B)
     //     second stream:                         | quadtree(B)            |
-    // (orbhip_set_blur_placement 1 / 2 are measurements of k_blur: they keep the two-kernel path)
-    const bool fusedDescribe = blurPlace == 0 && !fuseBlur && describe_blur_available(G, B);
+    //   two-kernel describe (k_blur + k_describe: denser batches, or ORBHIP_DESCRIBE_FUSED=0):
+    //     main stream  : FAST(all) | quadtree(A) | describe(A)            | describe(B)
+    //     second stream:           | blur(all)   | quadtree(B)            |
+    // 8 to 15 frames: one part (A is the whole batch, no quadtree(B)); the two-kernel blur still runs on the second stream.
+    // A frame or two: one cell per FAST workgroup (four times the workgroups, each a shorter chain -- the single-frame FAST
+    // time is one workgroup's latency), everything on one stream (a cross-stream hand-over costs more than it hides):
+    // quadtree, blur, describe.
+    const size_t blurFrame = c->lvl0FrameBytes + c->pyrFrameBytes;
+    const bool fusedDescribe = describe_blur_available(G, B);   // (never below 8 frames)
     auto blur_all = [&](hipStream_t st) {
         launch_blur(st, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_blur, blurFrame, c->d_blurTiles,
-                    fuseBlur ? c->blurLevelFirst[1] : (int)c->blurTiles.size(), c->d_blurBands, B);
+                    (int)c->blurTiles.size(), c->d_blurBands, B);
     };
     // quadtree / describe of the frames [b0, b0 + nb)
     const size_t qtPerFrame = B > 0 ? quadtree_table_scratch_bytes(G, 1) : 0;
@@ -393,13 +379,6 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
                         c->d_lvlKpCnt + (size_t)b0 * ORBHIP_MAX_LEVELS, c->d_lvlAngle + (size_t)b0 * G.totalKps, d_kps + (size_t)b0 * cap,
                         d_desc + (size_t)b0 * cap * 32, d_counts + b0, cap, nb, B < 8 ? c->describeMirror : 0);
     };
-    if (B >= 8 && blurPlace == 1) {
-        HIPCHK(c, hipEventRecord(c->evx[0], s));
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evx[0], 0));
-        if (ev) HIPCHK(c, hipEventRecord(c->evx[1], c->stream2));
-        blur_all(c->stream2);
-        HIPCHK(c, hipEventRecord(c->evx[2], c->stream2));
-    }
     if (B >= 8)
         launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_fastTiles, c->nFastTilesBatch, c->d_cand,
                     c->d_cellCnt, B, c->nFastTilesTall);
@@ -407,76 +386,42 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
         launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_fastTiles + c->nFastTilesBatch,
                     (int)c->fastTiles.size() - c->nFastTilesBatch, c->d_cand, c->d_cellCnt, B);
     if (evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));
-#ifndef DF_SCHED
-#define DF_SCHED 1
-#endif
-#ifndef DF_SPLIT
-#define DF_SPLIT 4
-#endif
-    static const bool noSplit = ORB_TUNE("NO_SPLIT", 0) != 0;   // A/B: r02 schedule
-    static const int fusedSched = ORB_TUNE("DESCRIBE_FUSED_SCHED", DF_SCHED);   // 1: quadtree(B) beside describe(A); 0: one quadtree launch
-    static const int fusedSplit = ORB_TUNE("DESCRIBE_FUSED_SPLIT", DF_SPLIT);   // eighths of the batch in the first part
-    if (fusedDescribe && B >= 16 && fusedSched >= 1) {
-        const int nA = std::max(8, B * fusedSplit / 8), nB = B - nA;
-        if (fusedSched == 2) {                                  // (A/B: both quadtree halves from the end of FAST, side by side)
-            if (!evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[2], 0));
-        }
-        quadtree_part(s, 0, nA);
-        HIPCHK(c, hipEventRecord(c->ev[3], s));                 // quadtree(A) is done: the second stream may start quadtree(B)
-        if (fusedSched == 1) HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[3], 0));
-        quadtree_part(c->stream2, nA, nB);
-        HIPCHK(c, hipEventRecord(c->evx[0], c->stream2));
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        describe_part(s, 0, nA);
-        HIPCHK(c, hipStreamWaitEvent(s, c->evx[0], 0));
-        describe_part(s, nA, nB);
-    } else if (fusedDescribe) {
-        quadtree_part(s, 0, B);
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        describe_part(s, 0, B);
-    } else if (B >= 16 && blurPlace == 0 && !noSplit) {
-        const int nA = B / 2, nB = B - nA;
-        if (!evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));   // (the hand-over event; the timing path has recorded it)
-        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[2], 0));
-        if (ev) HIPCHK(c, hipEventRecord(c->evx[1], c->stream2));
-        blur_all(c->stream2);
-        HIPCHK(c, hipEventRecord(c->evx[2], c->stream2));
-        quadtree_part(c->stream2, nA, nB);                      // behind the blur, i.e. beside describe(A)
-        HIPCHK(c, hipEventRecord(c->evx[0], c->stream2));
-        quadtree_part(s, 0, nA);
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        HIPCHK(c, hipStreamWaitEvent(s, c->evx[2], 0));         // the blur is done
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        describe_part(s, 0, nA);
-        HIPCHK(c, hipStreamWaitEvent(s, c->evx[0], 0));         // quadtree(B) is done
-        describe_part(s, nA, nB);
-    } else if (B >= 8) {
-        if (blurPlace == 0) {
-            if (!evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));
-            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[2], 0));
-            if (ev) HIPCHK(c, hipEventRecord(c->evx[1], c->stream2));
-            blur_all(c->stream2);
-            HIPCHK(c, hipEventRecord(c->evx[2], c->stream2));
-        } else if (blurPlace == 2) {
-            if (ev) HIPCHK(c, hipEventRecord(c->evx[1], s));
-            blur_all(s);
-            HIPCHK(c, hipEventRecord(c->evx[2], s));
-        }
-        quadtree_part(s, 0, B);
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[3], s));
-        if (blurPlace == 0 || blurPlace == 1) HIPCHK(c, hipStreamWaitEvent(s, c->evx[2], 0));
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        describe_part(s, 0, B);
-    } else {
+    const int nA = B >= 16 ? B / 2 : B, nB = B - nA;   // the two parts of the quadtree / describe
+    if (B < 8) {
         quadtree_part(s, 0, B);
         if (ev) HIPCHK(c, hipEventRecord(c->ev[3], s));
         if (ev) HIPCHK(c, hipEventRecord(c->evx[1], s));
         blur_all(s);
         if (ev) HIPCHK(c, hipEventRecord(c->evx[2], s));
-        if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
-        describe_part(s, 0, B);
+    } else if (fusedDescribe) {
+        quadtree_part(s, 0, nA);
+        if (nB > 0) {
+            HIPCHK(c, hipEventRecord(c->ev[3], s));             // quadtree(A) is done: the second stream may start quadtree(B)
+            HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[3], 0));
+            quadtree_part(c->stream2, nA, nB);
+            HIPCHK(c, hipEventRecord(c->evx[0], c->stream2));
+        } else if (ev) {
+            HIPCHK(c, hipEventRecord(c->ev[3], s));
+        }
+    } else {
+        if (!evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));   // (the hand-over event; the timing path has recorded it)
+        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[2], 0));
+        if (ev) HIPCHK(c, hipEventRecord(c->evx[1], c->stream2));
+        blur_all(c->stream2);
+        HIPCHK(c, hipEventRecord(c->evx[2], c->stream2));
+        if (nB > 0) {
+            quadtree_part(c->stream2, nA, nB);                  // behind the blur, i.e. beside describe(A)
+            HIPCHK(c, hipEventRecord(c->evx[0], c->stream2));
+        }
+        quadtree_part(s, 0, nA);
+        if (ev) HIPCHK(c, hipEventRecord(c->ev[3], s));
+        HIPCHK(c, hipStreamWaitEvent(s, c->evx[2], 0));         // the blur is done
+    }
+    if (ev) HIPCHK(c, hipEventRecord(c->ev[4], s));
+    describe_part(s, 0, nA);
+    if (nB > 0) {
+        HIPCHK(c, hipStreamWaitEvent(s, c->evx[0], 0));         // quadtree(B) is done
+        describe_part(s, nA, nB);
     }
     if (ev) HIPCHK(c, hipEventRecord(c->ev[5], s));
     if (pyrFork)
@@ -487,6 +432,7 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     if (!c->capturing) {
         c->haveStageEvents = ev;
         c->haveFastEvents = evFast;
+        c->haveBlurEvents = ev && !fusedDescribe;   // (k_describe_blur: no blur launch, no blur events)
         c->haveMatchEvents = false;
     }
     c->last_lvl0 = lvl0;
@@ -494,13 +440,6 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     c->last_frame0 = frame0;
     c->last_B = B;
     c->blurValid = !fusedDescribe;   // (orbhip_debug_get_blurred_level builds the blurred pyramid on request)
-    return ORBHIP_OK;
-}
-
-extern "C" int orbhip_set_blur_placement(orbhip_ctx *c, int place)
-{
-    if (!c || place < 0 || place > 2) return fail(c, ORBHIP_E_ARG, "orbhip_set_blur_placement: 0, 1 or 2");
-    c->blurPlace = place;
     return ORBHIP_OK;
 }
 
@@ -522,8 +461,8 @@ extern "C" int orbhip_get_stage_times(orbhip_ctx *c, float ms[6])
         HIPCHK(c, hipStreamSynchronize(c->stream2));
         HIPCHK(c, hipEventElapsedTime(&ms[0], c->ev[0], c->ev[1]));    // pyramid
         HIPCHK(c, hipEventElapsedTime(&ms[1], c->ev[1], c->ev[2]));    // FAST
-        HIPCHK(c, hipEventElapsedTime(&ms[2], c->ev[2], c->ev[3]));    // quadtree (overlaps the blur)
-        if (c->blurValid) HIPCHK(c, hipEventElapsedTime(&ms[3], c->evx[1], c->evx[2]));  // blur (second stream; none with k_describe_blur)
+        HIPCHK(c, hipEventElapsedTime(&ms[2], c->ev[2], c->ev[3]));    // quadtree (the first part only in a split batch)
+        if (c->haveBlurEvents) HIPCHK(c, hipEventElapsedTime(&ms[3], c->evx[1], c->evx[2]));  // blur (second stream in a batch)
         HIPCHK(c, hipEventElapsedTime(&ms[4], c->ev[4], c->ev[5]));    // describe
     }
     if (c->haveMatchEvents) HIPCHK(c, hipEventElapsedTime(&ms[5], c->ev[6], c->ev[7]));

@@ -272,7 +272,6 @@ int orb_build_geometry(orbhip_ctx *c, int w, int h, int stride0)
                 t.ncells = 1;
                 single.push_back(t);
             }
-        c->blurLevelFirst[l] = (int)c->blurTiles.size();
         for (int ty = 0; ty < (L.h + BLUR_TILE_H - 1) / BLUR_TILE_H; ty++)
             for (int tx = 0; tx < (L.w + BLUR_TILE_W - 1) / BLUR_TILE_W; tx++) {
                 BlurTile t;
@@ -283,7 +282,6 @@ int orb_build_geometry(orbhip_ctx *c, int w, int h, int stride0)
                 c->blurTiles.push_back(t);
             }
     }
-    c->blurLevelFirst[G.nlevels] = (int)c->blurTiles.size();
     // levels with cells taller than the fixed-layout kernel's first instance holds go to the end of the batch list (launch_fast)
     std::stable_partition(c->fastTiles.begin(), c->fastTiles.end(),
                           [&](const FastTile &t) { return G.lv[t.level].hCell + 6 <= FAST_FIX_ROWS; });

@@ -203,9 +203,8 @@ struct OrbPipe {
 struct orbhip_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr;   // blur runs here, concurrently with the quadtree kernel
-    hipEvent_t evx[3] = {nullptr, nullptr, nullptr};   // pyramid done (cross-stream hand-over) | blur start | blur end
-    int blurPlace = 0;               // where the blur runs in a batch (orbhip_set_blur_placement, include/orbhip.h)
+    hipStream_t stream2 = nullptr;   // batches: the second quadtree half (and the blur of the two-kernel schedule)
+    hipEvent_t evx[3] = {nullptr, nullptr, nullptr};   // cross-stream hand-over (quadtree(B) done; api_stereo) | blur start | blur end
     std::string err;
 
     // constructor tables (E0)
@@ -225,8 +224,6 @@ struct orbhip_ctx {
     int nFastTilesBatch = 0;
     int nFastTilesTall = 0;                       // ... of which the last nFastTilesTall belong to levels with cells taller than 34 rows
     std::vector<BlurTile> blurTiles;              // level by level
-    bool fuseBlurOk = false;                      // every level's k_resize_blur window fits (ORBHIP_FUSE_BLUR)
-    int blurLevelFirst[ORBHIP_MAX_LEVELS + 1] = {};   // first tile of every level (and the end)
     std::vector<ChainTile> chainTiles;            // chained pyramid of the single-frame path (empty = not available)
     std::vector<ChainGroup> chainGroups;
     ChainLevels chainLevels;
@@ -265,7 +262,7 @@ struct orbhip_ctx {
            cap_pnode = 0, cap_angle = 0, cap_cnt1 = 0, cap_cnt2 = 0, cap_cnt3 = 0;
 
     // state of the last extract call
-    bool blurValid = false;        // d_blur holds the blurred pyramid of the last call (false after a batch through k_describe_blur)
+    bool blurValid = false;        // d_blur holds the blurred pyramid of the last call (not after a batch through k_describe_blur)
     const uint8_t *last_lvl0 = nullptr;  // device pointer to level 0 of frame 0
     int last_stride0 = 0;
     size_t last_frame0 = 0;
@@ -309,6 +306,7 @@ struct orbhip_ctx {
     bool haveStageEvents = false, haveMatchEvents = false;
     int stageTiming = 2;     // orbhip_set_stage_timing: 2 = every stage (default), 1 = the FAST launch only, 0 = none
     bool haveFastEvents = false;
+    bool haveBlurEvents = false;   // evx[1] / evx[2] hold the blur launch of the last eager extract call with stage timing 2
 
     // rectification maps (orbhip_remap_set_maps): mapx then mapy, map_w * map_h floats each
     float *d_maps = nullptr;
@@ -366,10 +364,6 @@ void launch_quadtree(hipStream_t s, const OrbLevels &G, const uint32_t *cand, co
                      uint32_t *pts, uint32_t *pnode, int32_t *lvlCandCnt, uint32_t *lvlKp,
                      int32_t *lvlKpCnt, int B, uint8_t *tableScratch);
 size_t quadtree_table_scratch_bytes(const OrbLevels &G, int B);   // 0 when the node tables fit in LDS
-bool resize_blur_fits(const int32_t *xt, const int32_t *yt, int sw, int sh, int dw, int dh);
-void launch_resize_blur(hipStream_t s, const uint8_t *src, int sw, int sh, int sstride, size_t sframe, uint8_t *dst, int dw, int dh,
-                        int dstride, size_t dframe, uint8_t *bdst, int bstride, size_t bframe, const int32_t *ytab, const int32_t *gtab,
-                        const uint32_t *bands, int B);
 void launch_blur(hipStream_t s, const OrbLevels &G, const uint8_t *lvl0, int stride0, size_t frame0,
                  const uint8_t *pyr, size_t pyrFrame, uint8_t *blur, size_t blurFrame,
                  const BlurTile *tiles, int ntiles, const uint32_t *bands, int B);

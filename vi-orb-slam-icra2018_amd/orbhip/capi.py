@@ -16,11 +16,11 @@ CSRC = os.path.normpath(os.path.join(_HERE, "..", "csrc"))
 # what the C++ drop-in classes link -- loads the ablation build when one of those knobs is set in the environment (or with
 # ORBHIP_ABLATION=1), so that tests/ and tools/ reach the fallback paths; otherwise the product library.
 TUNE_KNOBS = (
-    "BLUR_PLACE", "NO_SPLIT", "COPY_OUT", "BOW_THREADS", "BOW_GLOBAL_DESC", "BOW_PHASES", "CHAIN_DEPTH", "DESCRIBE_KPW",
+    "COPY_OUT", "BOW_THREADS", "BOW_GLOBAL_DESC", "BOW_PHASES", "CHAIN_DEPTH", "DESCRIBE_KPW",
     "DESCRIBE_MAP", "DESCRIBE_PHASES", "DESCRIBE_PADLDS", "DESCRIBE_AX4", "PROJ_SEQ", "PROJ_ROUNDS", "PROJ_K", "INIT_K",
     "QT_THREADS", "QT_PHASES", "QT_LDSPTS", "QT_THREADS_SMALL", "SETS_COPY", "STEREO_ENT_PER_KP", "FAST_TILE_CELLS", "FAST_LISTCAP",
     "FAST_PHASES", "FAST_PITCH", "FAST_DEFER", "FAST_LDS_PAD", "XCD_MAP", "XCD_CHUNK", "FAST_XCD", "FRAME_SPLIT", "INIT_STOP",
-    "VOCAB_QUAD", "FUSE_BLUR", "RESIZE_FIT_P", "RESIZE_FIT", "RESIZE_LDS_PAD", "DESCRIBE_FUSED", "DESCRIBE_FUSED_SCHED", "DESCRIBE_FUSED_SPLIT", "BOW_LANE", "DEBUG_DESTROY",
+    "VOCAB_QUAD", "RESIZE_FIT_P", "RESIZE_FIT", "RESIZE_LDS_PAD", "DESCRIBE_FUSED", "BOW_LANE", "DEBUG_DESTROY",
 )
 
 
@@ -45,7 +45,7 @@ SYMBOLS = [
     "orbhip_pipe_create", "orbhip_pipe_destroy", "orbhip_pipe_submit", "orbhip_pipe_wait", "orbhip_pipe_enable_bow", "orbhip_pipe_matches",
     "orbhip_get_pyramid_level", "orbhip_set_host_pyramid", "orbhip_host_pyramid_level", "orbhip_debug_get_blurred_level", "orbhip_debug_get_candidates",
     "orbhip_debug_get_level_keypoints", "orbhip_hamming_knn2", "orbhip_hamming_knn2_device",
-    "orbhip_hamming_knn2_seq_device", "orbhip_get_stage_times", "orbhip_set_stage_timing", "orbhip_set_blur_placement", "orbhip_vocab_load", "orbhip_vocab_load_device",
+    "orbhip_hamming_knn2_seq_device", "orbhip_get_stage_times", "orbhip_set_stage_timing", "orbhip_vocab_load", "orbhip_vocab_load_device",
     "orbhip_vocab_info", "orbhip_vocab_text_to_binary", "orbhip_vocab_transform", "orbhip_vocab_transform_device",
     "orbhip_search_by_bow_seq_device", "orbhip_stereo_match", "orbhip_stereo_match_device",
     "orbhip_hamming_knn2_lists", "orbhip_search_by_bow", "orbhip_comm_unique_id",
@@ -132,7 +132,6 @@ def load():
     L.orbhip_hamming_knn2_seq_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.orbhip_get_stage_times.argtypes = [vp, vp]
     L.orbhip_set_stage_timing.argtypes = [vp, i32]
-    L.orbhip_set_blur_placement.argtypes = [vp, i32]
     L.orbhip_stereo_match.argtypes = [vp, vp, vp, vp, i32, vp, vp, i32, f32, f32, vp, vp, ip]
     L.orbhip_stereo_match_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp]
     L.orbhip_vocab_load.argtypes = [vp, vp, C.c_size_t]

@@ -581,6 +581,73 @@ int orbhip_knn2_allgather_merge_device(orbhip_ctx *ctx, const void *d_best_idx_l
 int orbhip_knn2_merge_device(orbhip_ctx *ctx, const void *d_parts, int nshards, int nq, void *d_best_idx, void *d_best_d,
                              void *d_second_d);
 
+/* ---- key-frame database (ref: src/KeyFrameDatabase.cc) ----
+ * The BoW inverted file that picks the key frames relocalisation (src/Tracking.cc:2573) and loop detection
+ * (src/LoopClosing.cc:193) match against, resident on the device (DESIGN.md "Key-frame database").  Key frames are named by a
+ * caller-chosen 64-bit key (the drop-in uses KeyFrame::mnId).  BowVectors are (word[n] ascending, value[n]) pairs as
+ * ORBVocabulary::transform returns them; n <= 8192 words per BowVector.  Results are bit for bit those of the reference:
+ * candidate order, the (int)(max * 0.8f) threshold, the L1 score summed in double over the common words in ascending id
+ * (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-67) and narrowed to float, the float covisibility sums in list order.
+ * Divergences from the reference, by design:
+ *   - adding a key that is already present returns ORBHIP_E_ARG (the reference would insert the key frame twice);
+ *   - every query is a fresh query: no query id is taken (the reference would double-count mnRelocWords when asked twice
+ *     with the same Frame::mnId);
+ *   - the stale score of a reloc query (a covisible key frame that shares a word but was not scored adds its mRelocScore of
+ *     an earlier query, ref :241-268) is kept per key; a key frame never scored has 0 (the reference reads an uninitialised
+ *     field, src/KeyFrame.cc:58); erase or clear forget it;
+ *   - excluded keys (the loop query's GetConnectedKeyFrames(), ref :82-104) are honoured in both modes.
+ * Limits: max_kfs <= 4194304 key frames (ORBHIP_E_CAPACITY when full), 8192 words per BowVector (ORBHIP_E_SIZE), B <= 1024
+ * queries per batch (ORBHIP_E_SIZE), word ids below nwords and strictly ascending (ORBHIP_E_ARG).  Nothing is truncated.
+ * Memory: the database holds ~60 bytes per key frame plus 12 per BowVector word (twice while a rebuild runs); a query call
+ * keeps dense per-(query, key frame) state of B x max_kfs x 37 bytes plus B x 64 KB, allocated on the first call of that
+ * batch size and kept: 2.4 GB for B = 1024 at max_kfs = 65536.  A batch that does not fit returns ORBHIP_E_HIP.
+ * A query call that fails (invalid query, output too small) leaves the database as it was -- the stale reloc scores
+ * included -- so the same call with a larger output returns what it would have returned the first time. */
+#define ORBHIP_KFDB_RELOC 0   /* DetectRelocalizationCandidates (ref :199-311) */
+#define ORBHIP_KFDB_LOOP 1    /* DetectLoopCandidates (ref :78-197) */
+/* Replaces KeyFrameDatabase::KeyFrameDatabase(const ORBVocabulary&) (ref :33-37): an empty database over `nwords` words
+ * (ORBVocabulary::size()) for at most max_kfs key frames.  delta_max: key frames added between two rebuilds of the inverted
+ * file (0 = 128).  Calling it again drops the old database. */
+int orbhip_kfdb_init(orbhip_ctx *ctx, int nwords, int max_kfs, int delta_max);
+/* Replaces KeyFrameDatabase::add (ref :40-46): the key frame's BowVector joins every word's list after the key frames added
+ * before it. */
+int orbhip_kfdb_add(orbhip_ctx *ctx, uint64_t key, const uint32_t *word, const double *value, int n);
+/* Replaces KeyFrameDatabase::erase (ref :48-68); an absent key is not an error.  clear (ref :70-74) empties the database. */
+int orbhip_kfdb_erase(orbhip_ctx *ctx, uint64_t key);
+int orbhip_kfdb_clear(orbhip_ctx *ctx);
+/* The key frame's KeyFrame::GetBestCovisibilityKeyFrames(10) as keys, best first (n <= 10); read by orbhip_kfdb_detect*.
+ * Neighbours need not be in the database. Reset by add. */
+int orbhip_kfdb_set_covis(orbhip_ctx *ctx, uint64_t key, const uint64_t *neigh, int n);
+/* Key frames in the database, in the delta region, erased but not yet folded out; rebuilds so far.  Any pointer may be NULL. */
+int orbhip_kfdb_info(orbhip_ctx *ctx, int *live, int *delta, int *tombs, long long *rebuilds);
+/* The first half of one query (ref :82-137 loop, :203-239 reloc), for the C++ drop-in, which runs the covisibility step on its
+ * own KeyFrame objects: every key frame that shares a word with the BowVector, excluded ones included, in the reference's
+ * order (lKFsSharingWords, excluded ones at the place they were first met), with its shared-word count and its score (0 when
+ * it was not scored: excluded, or count <= *min_common).  *nout = number of such key frames; ORBHIP_E_CAPACITY when it
+ * exceeds cap (the first cap are filled).  A reloc-mode call also updates the stale scores. */
+int orbhip_kfdb_score(orbhip_ctx *ctx, int mode, const uint32_t *word, const double *value, int n, const uint64_t *excluded,
+                      int nx, uint64_t *keys, int32_t *counts, float *scores, int cap, int *nout, int *min_common);
+/* Replaces DetectLoopCandidates(pKF, minScore) / DetectRelocalizationCandidates(F) (ref :78-311) for B queries at once,
+ * exactly as B calls in batch order (stale reloc scores pass from query b to b + 1).  Queries as CSR (qoff[B + 1], qword,
+ * qvalue), excluded keys per query as CSR (xoff[B + 1], xkey; xoff may be NULL on the host entry point), min_score for the
+ * loop mode.  Candidates as CSR: out_off[B + 1], out_keys[out_off[B]]; ORBHIP_E_CAPACITY when out_off[B] > out_cap (out_off
+ * is still filled, nothing changed: call again with out_cap >= out_off[B]).  orbhip_kfdb_detect_device takes device pointers
+ * (xoff not NULL) and, unlike other *_device entry points, synchronises: it reads qoff[0], qoff[B], xoff[0], xoff[B] before the
+ * launches (ORBHIP_E_ARG unless both start at 0) and the status word and out_off[B] after them (limits are checked on the
+ * device); ORBHIP_E_CAPACITY as the host entry point. */
+int orbhip_kfdb_detect(orbhip_ctx *ctx, int mode, int B, const int32_t *qoff, const uint32_t *qword, const double *qvalue,
+                       const int32_t *xoff, const uint64_t *xkey, float min_score, int32_t *out_off, uint64_t *out_keys,
+                       int out_cap);
+int orbhip_kfdb_detect_device(orbhip_ctx *ctx, int mode, int B, const void *d_qoff, const void *d_qword, const void *d_qvalue,
+                              const void *d_xoff, const void *d_xkey, float min_score, void *d_out_off, void *d_out_keys,
+                              int out_cap);
+/* Phase timing of the query calls (no counterpart in the reference): with timing on, every orbhip_kfdb_score / _detect /
+ * _detect_device records HIP events at its phase boundaries; orbhip_kfdb_phase_times gives the last call's six phase times in
+ * ms: 0 inverted-file walk (with validation, exclusion and the delta region), 1 max count, 2 scores, 3 reference order,
+ * 4 covisibility accumulation, 5 retention + output (4 and 5 are 0 for orbhip_kfdb_score). */
+int orbhip_kfdb_set_timing(orbhip_ctx *ctx, int on);
+int orbhip_kfdb_phase_times(orbhip_ctx *ctx, float *ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,28 @@ public:
     void CopyGridFrom(const Frame &F);            // the grid part of KeyFrame::KeyFrame(Frame &F, ...)
     std::vector<size_t> GetFeaturesInArea(const float &x, const float &y, const float &r) const;
     bool IsInImage(const float &x, const float &y) const { return (x>=mnMinX && x<mnMaxX && y>=mnMinY && y<mnMaxY); }
+
+    // read and written by KeyFrameDatabase (ref: include/KeyFrame.h:240-245, src/KeyFrameDatabase.cc); initialised to 0 here
+    // (the reference leaves mRelocScore uninitialised, src/KeyFrame.cc:58)
+    DBoW2::BowVector mBowVec;
+    long unsigned int mnLoopQuery = 0;
+    int mnLoopWords = 0;
+    float mLoopScore = 0;
+    long unsigned int mnRelocQuery = 0;
+    int mnRelocWords = 0;
+    float mRelocScore = 0;
+    // the covisibility graph as KeyFrameDatabase reads it (ref: src/KeyFrame.cc GetConnectedKeyFrames /
+    // GetBestCovisibilityKeyFrames over mvpOrderedConnectedKeyFrames): key frames by decreasing weight, filled by the caller
+    std::vector<KeyFrame *> mvpOrderedConnectedKeyFrames;
+    std::set<KeyFrame *> GetConnectedKeyFrames()
+    {
+        return std::set<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.end());
+    }
+    std::vector<KeyFrame *> GetBestCovisibilityKeyFrames(const int &N)
+    {
+        if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+        return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+    }
 };
 
 inline int MapPoint::PredictScale(const float &currentDist, KeyFrame *pKF)

@@ -68,6 +68,8 @@ int orb_bow_rotation_check(const int32_t *pairs, int npairs, const int32_t *off1
                            const float *angle2, int check_ori, int32_t *match12, int32_t *match21);
 // api_sets.hip
 void orb_sets_release(orbhip_ctx *c);
+// api_kfdb.hip
+void orb_kfdb_release(orbhip_ctx *c);
 static inline bool grid_params_ok(float inv_w, float inv_h) { return inv_w > 0.f && inv_h > 0.f; }
 
 // Bump allocator over one temporary device block (host-pointer matching entry points).

@@ -205,6 +205,7 @@ extern "C" void orbhip_destroy(orbhip_ctx *c)
     orb_pipe_release(c);
     step("comm/pipe");
     orb_sets_release(c);
+    orb_kfdb_release(c);
     step("sets");
     orb_graph_release(c);
     step("graph");

@@ -322,6 +322,8 @@ struct orbhip_ctx {
     OrbPipe *pipe = nullptr;
     // resident feature sets (api_sets.hip)
     void *setTable = nullptr;
+    // key-frame database (api_kfdb.hip)
+    void *kfdb = nullptr;
     // orbhip_frame_build (api_frame.hip): the Frame constructor's device work as one captured graph
     void *frameBuild = nullptr;
     long long describeMirror = 0;     // != 0 while orbhip_frame_build enqueues: k_describe<.., MIRROR> stores its results twice

@@ -59,6 +59,8 @@ SYMBOLS = [
     "orbhip_remap_set_maps", "orbhip_remap", "orbhip_remap_device",
     "orbhip_set_put", "orbhip_set_has", "orbhip_set_drop", "orbhip_search_by_bow_sets", "orbhip_window_best_set",
     "orbhip_set_info", "orbhip_set_fingerprint", "orbhip_set_fingerprint_rows", "orbhip_vocab_share", "orbhip_vocab_generation", "orbhip_set_limit", "orbhip_debug_roundtrip", "orbhip_debug_path_mask", "orbhip_frame_build", "orbhip_frame_fingerprint", "orbhip_set_put_from_frame",
+    "orbhip_kfdb_init", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_clear", "orbhip_kfdb_set_covis", "orbhip_kfdb_info",
+    "orbhip_kfdb_score", "orbhip_kfdb_detect", "orbhip_kfdb_detect_device", "orbhip_kfdb_set_timing", "orbhip_kfdb_phase_times",
 ]
 
 
@@ -195,6 +197,18 @@ def load():
     L.orbhip_comm_info.argtypes = [vp, ip, ip]
     L.orbhip_knn2_allgather_merge_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp]
     L.orbhip_knn2_merge_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    u64 = C.c_uint64
+    L.orbhip_kfdb_init.argtypes = [vp, i32, i32, i32]
+    L.orbhip_kfdb_add.argtypes = [vp, u64, vp, vp, i32]
+    L.orbhip_kfdb_erase.argtypes = [vp, u64]
+    L.orbhip_kfdb_clear.argtypes = [vp]
+    L.orbhip_kfdb_set_covis.argtypes = [vp, u64, vp, i32]
+    L.orbhip_kfdb_info.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_longlong)]
+    L.orbhip_kfdb_score.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, ip, ip]
+    L.orbhip_kfdb_detect.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32]
+    L.orbhip_kfdb_detect_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32]
+    L.orbhip_kfdb_set_timing.argtypes = [vp, i32]
+    L.orbhip_kfdb_phase_times.argtypes = [vp, vp]
     _lib = L
     return L
 

@@ -177,16 +177,15 @@ def test_alternative_code_paths_give_the_same_results(env):
 
 
 @pytest.mark.parametrize("env", [
-    {"ORBHIP_FAST_FIX": "0"},                 # the generic FAST kernel (any cell grid) instead of the fixed-layout one
-    {"ORBHIP_FAST_DEFER": "0"},               # fixed-layout kernel: both polarities of a work-list entry in place
-    {"ORBHIP_FAST_TILE_CELLS": "5"},          # runs of five cells (wave 0 finishes two cells)
-    {"ORBHIP_FAST_TILE_CELLS": "2"},
-    {"ORBHIP_FAST_LISTCAP": "24"},            # every list overflows: dense scoring, score-tile scans, the wave-local fallbacks of pass 1
-    {"ORBHIP_FAST_LISTCAP": "24", "ORBHIP_FAST_FIX": "0"},
-    {"ORBHIP_DESCRIBE_AX4": "0"},             # angle phase of the batch describe kernel: five dword loads + masks instead of one dwordx4 load + constant weights
-    {"ORBHIP_DESCRIBE_KPW": "32"},            # ... 32 slots per workgroup (always the dword form)
-    pytest.param({"ORBHIP_RESIZE_FIT": "0"}, id="env10"),   # k_resize<32> (128 x 32 tiles), what a level keeps when no fitted geometry
-                                                            # passes the window check (the id it had when the list held three more cases)
+    # (each case keeps the id it had when the list held five more)
+    pytest.param({"ORBHIP_FAST_FIX": "0"}, id="env0"),          # the generic FAST kernel (any cell grid) instead of the fixed-layout one
+    pytest.param({"ORBHIP_FAST_TILE_CELLS": "5"}, id="env2"),   # runs of five cells (wave 0 finishes two cells)
+    pytest.param({"ORBHIP_FAST_TILE_CELLS": "2"}, id="env3"),
+    pytest.param({"ORBHIP_FAST_LISTCAP": "24"}, id="env4"),     # every list overflows: dense scoring, score-tile scans, the wave-local
+                                                                # fallbacks of pass 1
+    pytest.param({"ORBHIP_FAST_LISTCAP": "24", "ORBHIP_FAST_FIX": "0"}, id="env5"),
+    pytest.param({"ORBHIP_RESIZE_FIT": "0"}, id="env10"),       # k_resize<32> (128 x 32 tiles), what a level keeps when no fitted
+                                                                # geometry passes the window check
 ])
 def test_alternative_batch_code_paths_give_the_same_results(env):
     """The switchable choices of the BATCH path (read once per process): 16-frame batches of two geometries -- one inside the

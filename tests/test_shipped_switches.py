@@ -24,10 +24,34 @@ def test_shipped_library_has_only_the_four_switches():
         assert not any(banned in l for l in lines), (banned, lines)
 
 
-def test_ablation_library_has_the_knobs():
+def test_ablation_library_reads_every_tune_knob():
+    """Every name of capi.TUNE_KNOBS (= every ORB_TUNE name in csrc/, test_binding_knob_list_matches_the_sources) is an
+    environment variable the ablation build reads."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "vi-orb-slam-icra2018_amd"))
+    from orbhip import capi
     names = {l for l in _env_names("liborbhip_ablation.so") if re.fullmatch(r"ORBHIP_[A-Z0-9_]+", l)}
-    for k in ("ORBHIP_FAST_PHASES", "ORBHIP_FAST_LISTCAP", "ORBHIP_DESCRIBE_PHASES", "ORBHIP_PROJ_K", "ORBHIP_FAST_XCD"):
+    for k in ("ORBHIP_FAST_PHASES", "ORBHIP_FAST_LISTCAP", "ORBHIP_DESCRIBE_PHASES", "ORBHIP_PROJ_K", "ORBHIP_QT_PHASES"):
         assert k in names, (k, names)
+    for k in capi.TUNE_KNOBS:
+        assert "ORBHIP_" + k in names, (k, names)
+
+
+def test_binding_knob_list_matches_the_sources():
+    """capi.TUNE_KNOBS (which knobs make the binding load the ablation build) is exactly the set of ORB_TUNE names in csrc/, and
+    ORB_SWITCH names only the four shipped switches: a knob added or removed in the sources without the list fails here."""
+    import glob
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "vi-orb-slam-icra2018_amd"))
+    from orbhip import capi
+    tune, switch = set(), set()
+    for path in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")):
+        src = open(path).read()
+        tune |= set(re.findall(r'ORB_TUNE\("([A-Z0-9_]+)"', src))
+        switch |= set(re.findall(r'ORB_SWITCH\("([A-Z0-9_]+)"', src))
+    assert len(capi.TUNE_KNOBS) == len(set(capi.TUNE_KNOBS)), capi.TUNE_KNOBS
+    assert set(capi.TUNE_KNOBS) == tune, (set(capi.TUNE_KNOBS) - tune, tune - set(capi.TUNE_KNOBS))
+    assert {"ORBHIP_" + n for n in switch} == SHIPPED, switch
 
 
 def test_binding_picks_the_ablation_build_only_when_asked():

@@ -191,26 +191,14 @@ extern "C" orbhip_ctx *orbhip_create(int device, int nfeatures, float scaleFacto
 extern "C" void orbhip_destroy(orbhip_ctx *c)
 {
     if (!c) return;
-    static const int dbg = ORB_TUNE("DEBUG_DESTROY", 0);   // (ablation build: which step leaves a sticky HIP error behind?)
-    auto step = [&](const char *what) {
-        if (!dbg) return;
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) fprintf(stderr, "orbhip_destroy: sticky HIP error after %s: %s\n", what, hipGetErrorString(e));
-    };
-    step("entry");
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    step("sync");
     orb_comm_release(c);
     orb_pipe_release(c);
-    step("comm/pipe");
     orb_sets_release(c);
     orb_kfdb_release(c);
-    step("sets");
     orb_graph_release(c);
-    step("graph");
     orb_frame_release(c);
-    step("frame");
     if (c->h_in) (void)hipHostFree(c->h_in);
     if (c->h_pyr) (void)hipHostFree(c->h_pyr);
     void *bufs[] = {c->d_lvl0, c->d_pyr, c->d_blur, c->d_cand, c->d_cellCnt, c->d_pts, c->d_pnode,
@@ -227,10 +215,8 @@ extern "C" void orbhip_destroy(orbhip_ctx *c)
         if (c->evx[i]) (void)hipEventDestroy(c->evx[i]);
     for (int i = 0; i < 2; i++)
         if (c->evp[i]) (void)hipEventDestroy(c->evp[i]);
-    step("events");
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    step("streams");
     // Best-effort clean-up must not leave the runtime's sticky last error behind for whatever the thread calls next: e.g.
     // hipEventSynchronize on a busy event whose recording stream -- another context's, destroyed before this one -- is gone can
     // report "operation not permitted on an event last recorded in a capturing stream" (seen twice in 4440 soak configurations, r06;
@@ -570,9 +556,7 @@ static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B,
         else
             for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * s0, imgs[b] + (size_t)y * stride, (size_t)w);
     }
-    uint8_t *blk = reinterpret_cast<uint8_t *>(c->d_kps);
-    static const bool directOut = ORB_TUNE("COPY_OUT", 0) == 0;   // A/B: 1 = result copy node
-    const void *key[5] = {c->d_lvl0, blk, c->h_in, c->h_stage, hpyr};
+    const void *key[5] = {c->d_lvl0, c->d_kps, c->h_in, c->h_stage, hpyr};
     const bool same = c->g_exec && c->g_w == w && c->g_h == h && c->g_B == B && c->g_gen == c->allocGen &&
                       memcmp(key, c->g_key, sizeof(key)) == 0;
     if (!same) {
@@ -582,12 +566,11 @@ static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B,
         HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         // the describe kernel writes keypoints, descriptors and counts straight into the page-locked result block (posted PCIe
         // writes of a few dozen KB that overlap the kernel): no copy node behind it -- that node started 8 us after describe ended
-        uint8_t *out = directOut ? c->h_stage : blk;
+        uint8_t *out = c->h_stage;
         hipError_t e = hipMemcpyAsync(c->d_lvl0, c->h_in, inBytes, hipMemcpyHostToDevice, c->stream);
         rc = e == hipSuccess ? orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
                                             (int32_t *)(out + coff), dcap, hpyr)
                              : ORBHIP_E_HIP;
-        if (rc == ORBHIP_OK && !directOut) e = hipMemcpyAsync(c->h_stage, blk, coff + cbytes, hipMemcpyDeviceToHost, c->stream);
         hipGraph_t g = nullptr;
         const hipError_t e2 = hipStreamEndCapture(c->stream, &g);
         c->capturing = false;
@@ -607,12 +590,11 @@ static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B,
     if ((c->g_calls++ & 255u) == 0) {
         // the first call of a geometry and every 256th one run the same chain eagerly: that refreshes the stage times behind
         // GetTimeOfComputePyramid / ...KeyPointsOctTree / ...Descriptor (include/ORBextractor.h:51-53)
-        uint8_t *out = directOut ? c->h_stage : blk;
+        uint8_t *out = c->h_stage;
         HIPCHK(c, hipMemcpyAsync(c->d_lvl0, c->h_in, inBytes, hipMemcpyHostToDevice, c->stream));
         if ((rc = orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
                                (int32_t *)(out + coff), dcap, hpyr)))
             return rc;
-        if (!directOut) HIPCHK(c, hipMemcpyAsync(c->h_stage, blk, coff + cbytes, hipMemcpyDeviceToHost, c->stream));
     } else {
         HIPCHK(c, hipGraphLaunch(c->g_exec, c->stream));
     }

@@ -382,8 +382,8 @@ void launch_blur(hipStream_t s, const OrbLevels &G, const uint8_t *lvl0, int str
 {
     if (ntiles <= 0) return;
     orb_path(ORB_PATH_BLUR);
-    dim3 grid(orb_xcd_grid((ntiles + BM_TPW - 1) / BM_TPW, 2), B, 1), block(256, 1, 1);
+    dim3 grid(orb_xcd_pad((ntiles + BM_TPW - 1) / BM_TPW), B, 1), block(256, 1, 1);   // XCD mode 2 (orbhip_internal.h)
     hipLaunchKernelGGL(k_blur, grid, block, 0, s, G, lvl0, stride0, (unsigned long long)frame0, pyr,
                        (unsigned long long)pyrFrame, blur, (unsigned long long)blurFrame, tiles,
-                       reinterpret_cast<const uint4 *>(bands), orb_xcd_arg(2), ntiles);
+                       reinterpret_cast<const uint4 *>(bands), 2, ntiles);
 }

@@ -25,11 +25,7 @@
 
 #define BS_HISTO 30
 
-static int bs_threads()
-{
-    static const int n = ORB_TUNE("BOW_THREADS", 1024);
-    return n;
-}
+#define BS_THREADS 1024   // threads per workgroup of k_bow_seq (its launch bound)
 
 // 16 bytes per lane from global memory straight into LDS at (ldsAddr + 16 * lane); M0 carries the LDS address and is restored
 __device__ __forceinline__ void bs_glds16(const void *gsrc, uint32_t ldsAddr)
@@ -103,7 +99,7 @@ __device__ void bs_sort2(unsigned long long *keysA, unsigned long long *keysB, i
 // LDSD: both descriptor sets are staged in LDS (fits for cap up to ~1500 keypoints per frame); otherwise they
 // are read from global memory.
 template <bool LDSD>
-__global__ __launch_bounds__(1024) void k_bow_seq(const uint8_t *__restrict__ desc,
+__global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restrict__ desc,
                                                  const orbhip_keypoint *__restrict__ kps,
                                                  const int32_t *__restrict__ counts,
                                                  const int32_t *__restrict__ node, const float *__restrict__ weight,
@@ -1128,10 +1124,10 @@ hipError_t launch_bow_seq(hipStream_t s, const uint8_t *desc, const orbhip_keypo
     }
     orb_path(ldsd ? ORB_PATH_BOW_SEQ_LDS : ORB_PATH_BOW_SEQ_GLOBAL);
     if (ldsd)
-        hipLaunchKernelGGL(k_bow_seq<true>, dim3(B, 1, 1), dim3(bs_threads(), 1, 1), lds, s, desc, kps, counts, node, weight, valid,
+        hipLaunchKernelGGL(k_bow_seq<true>, dim3(B, 1, 1), dim3(BS_THREADS, 1, 1), lds, s, desc, kps, counts, node, weight, valid,
                            cap, NP, lag, th, th_mode, nnratio, check_ori, match12, match21, nmatches ORB_ABL_ARG(dbg));
     else
-        hipLaunchKernelGGL(k_bow_seq<false>, dim3(B, 1, 1), dim3(bs_threads(), 1, 1), lds, s, desc, kps, counts, node, weight, valid,
+        hipLaunchKernelGGL(k_bow_seq<false>, dim3(B, 1, 1), dim3(BS_THREADS, 1, 1), lds, s, desc, kps, counts, node, weight, valid,
                            cap, NP, lag, th, th_mode, nnratio, check_ori, match12, match21, nmatches ORB_ABL_ARG(dbg));
     return hipGetLastError();
 }

@@ -73,23 +73,22 @@ __device__ __forceinline__ int wave_sum(int v)
 //      sequence is evaluated once per keypoint by one lane instead of once per wave by 64 lanes;
 //   C. wave per keypoint again: the lane's four test pairs are decoded once (16 floats), then per keypoint 4 x
 //      (rotate, round, two byte gathers from the blurred level, compare, ballot).
-// DS_KP = slots per workgroup: 16 for batches (see DESCRIBE_DEFAULT_MAP below), 8 for a single frame or two (more
-// workgroups, shorter serial chains per wave: latency); 32 remains for A/B runs (ORBHIP_DESCRIBE_KPW)
+// DS_KP = slots per workgroup: 16 for batches (see the placement below), 8 for a single frame or two (more workgroups, shorter
+// serial chains per wave: latency)
 #define DS_R 18                       // pattern radius <= 18.385, so a rotated, rounded coordinate is at most 18
 #define DS_ROWS (2 * DS_R + 1)        // 37 patch rows
 #define DS_PDW 10                     // dwords per staged row: 37 bytes + up to 3 bytes of alignment
 #define DS_TRIPS ((DS_ROWS * DS_PDW + 63) / 64)   // 6
 
-// Default placement: a whole frame per XCD (xcd_frame_tile) with 16 keypoint slots per workgroup, so that the workgroups
+// Placement (XCD mode 4): a whole frame per XCD (xcd_frame_tile) with 16 keypoint slots per workgroup, so that the workgroups
 // resident on one XCD at a time (224 of them) work on three or four frames and the raw + blurred pyramids of those frames
 // (1.9 MB each) are served by that XCD's 4 MB L2: L2 hit rate 51 % -> ~70 %, fabric reads 5.1 GB -> ~2.4 GB per 1024-frame
 // launch, 0.79 -> 0.74 ms (profiles/r02a/describe.md).  Fewer slots per workgroup cut the traffic further (8: 1.95 GB =
 // every pyramid byte once) but cost more in per-workgroup set-up than they gain: the kernel is bound by the number of
 // 128-byte lines its row gathers touch (~88 per keypoint), not by where they come from.
-#define DESCRIBE_DEFAULT_MAP 4
 typedef const __attribute__((address_space(3))) uint8_t *lds_u8p;
 
-// Angle phase, batches: the whole 31 x 31 disc in ONE load instruction -- lane (row = lane >> 1, half = lane & 1) takes the 16 bytes
+// Angle phase, 16 slots (batches): the whole 31 x 31 disc in ONE load instruction -- lane (row = lane >> 1, half = lane & 1) takes the 16 bytes
 // from column cx - 15 + 16 half of disc row `row` (byte-aligned dwordx4; 32 adjacent bytes per row) -- and per-lane constant byte
 // weights instead of per-keypoint masks: the load starts at the disc's own first column, so which bytes of a lane lie inside the
 // disc, and their u, never change.  wu = u + 16 inside the disc (1..31), 0 outside; wm = 1 inside, 0 outside:
@@ -125,7 +124,7 @@ struct __attribute__((packed, aligned(1))) UnalignedU4 {
 // MIRROR: every result (count, keypoint records, descriptors) is stored a second time `mirror` bytes further on -- the page-locked
 // twin of the device block the results go to (orbhip_frame_build: the kernels behind this one read the device copy, the host reads
 // the twin without a copy command in between).  Instantiated for the single-frame kernel only.
-template <int DS_KP, bool AX4, bool MIRROR = false>
+template <int DS_KP, bool MIRROR = false>
 __global__ __launch_bounds__(256, 8) void k_describe(const OrbLevels G, const uint8_t *__restrict__ lvl0,
                                                   int stride0, unsigned long long frame0,
                                                   const uint8_t *__restrict__ pyr,
@@ -197,7 +196,7 @@ __global__ __launch_bounds__(256, 8) void k_describe(const OrbLevels G, const ui
     ORB_ABL_STOP(phases < 1);   // timing ablation only (liborbhip_ablation.so, ORBHIP_DESCRIBE_PHASES): results are then invalid
 
     // ---- A. E5: IC_Angle moments on the un-blurred level ----
-    if constexpr (AX4) {
+    if constexpr (DS_KP == 16) {   // the one-load form: written for the umax table of a 31-pixel patch (angle_umax_is_31)
         const uint4 wu = *reinterpret_cast<const uint4 *>(&c_angle_wt.wu[lane][0]);
         const uint4 wm = *reinterpret_cast<const uint4 *>(&c_angle_wt.wm[lane][0]);
         const int rowc = min(lane >> 1, 2 * ORB_HALF_PATCH), half16 = 16 * (lane & 1), vrow = (lane >> 1) - ORB_HALF_PATCH;
@@ -960,17 +959,22 @@ __global__ __launch_bounds__(256, DF_WG_PER_CU) void k_describe_blur(const OrbLe
     }
 }
 
-// Can a batch of this geometry take k_describe_blur (the blurred pyramid is then never built)?  The kernel is written for the umax
-// table of a 31-pixel patch (always what orb_init_tables computes) and for 16 slots per workgroup.  ORBHIP_DESCRIBE_FUSED=0
+// The one-load angle phase (k_describe<16>, k_describe_blur) is written for the umax table of a 31-pixel patch -- always what
+// orb_init_tables computes; any other table takes k_blur + k_describe<8>.
+static bool angle_umax_is_31(const OrbLevels &G)
+{
+    static const int umaxWant[16] = {ANGLE_UMAX_VALUES};
+    for (int v = 0; v < 16; v++)
+        if (G.umax[v] != umaxWant[v]) return false;
+    return true;
+}
+
+// Can a batch of this geometry take k_describe_blur (the blurred pyramid is then never built)?  ORBHIP_DESCRIBE_FUSED=0
 // (liborbhip_ablation.so): k_blur + k_describe for batches too.
 bool describe_blur_available(const OrbLevels &G, int B)
 {
     static const int fusedEnv = ORB_TUNE("DESCRIBE_FUSED", 1);
-    static const int kpwEnv = ORB_TUNE("DESCRIBE_KPW", 0);
-    static const int ax4Env = ORB_TUNE("DESCRIBE_AX4", 1);
-    static const int umaxWant[16] = {ANGLE_UMAX_VALUES};
-    bool ok = fusedEnv != 0 && B >= 8 && ax4Env != 0 && (kpwEnv == 0 || kpwEnv == 16);
-    for (int v = 0; v < 16; v++) ok = ok && G.umax[v] == umaxWant[v];
+    bool ok = fusedEnv != 0 && B >= 8 && angle_umax_is_31(G);
     long long px = 0;
     for (int l = 0; l < G.nlevels; l++) {
         ok = ok && G.lv[l].w >= 48 && G.lv[l].h >= 40 && G.lv[l].w < 65536 && G.lv[l].h < 32768;
@@ -988,16 +992,13 @@ void launch_describe_blur(hipStream_t s, const OrbLevels &G, const uint8_t *lvl0
                           size_t pyrFrame, const uint32_t *lvlKp, const int32_t *lvlKpCnt, float *lvlAngle, orbhip_keypoint *kps,
                           uint8_t *desc, int32_t *counts, int cap, int B)
 {
-    static const int dmap = ORB_TUNE("DESCRIBE_MAP", -1);
-    const int mapArg = dmap >= 0 ? (dmap | (orb_xcd_chunk() << 8)) : orb_xcd_arg(DESCRIBE_DEFAULT_MAP);
     static const int phases = ORB_TUNE("DESCRIBE_PHASES", 4);
     (void)phases;
-    const int nblk = (G.totalKps + DF_KP - 1) / DF_KP;
-    dim3 grid((mapArg & 255) ? (nblk + 7) / 8 * 8 : nblk, B, 1), block(256, 1, 1);
+    dim3 grid(orb_xcd_pad((G.totalKps + DF_KP - 1) / DF_KP), B, 1), block(256, 1, 1);   // XCD mode 4
     orb_path(ORB_PATH_DESCRIBE_BLUR);
     static const int padLds = ORB_TUNE("DESCRIBE_PADLDS", 0);   // occupancy experiment only: unused dynamic LDS caps the workgroups per CU
     hipLaunchKernelGGL(k_describe_blur, grid, block, (size_t)padLds, s, G, lvl0, stride0, (unsigned long long)frame0, pyr, (unsigned long long)pyrFrame,
-                       lvlKp, lvlKpCnt, lvlAngle, kps, desc, counts, cap, mapArg ORB_ABL_ARG(phases));
+                       lvlKp, lvlKpCnt, lvlAngle, kps, desc, counts, cap, 4 ORB_ABL_ARG(phases));
 }
 
 void launch_describe(hipStream_t s, const OrbLevels &G, const uint8_t *lvl0, int stride0, size_t frame0,
@@ -1006,36 +1007,21 @@ void launch_describe(hipStream_t s, const OrbLevels &G, const uint8_t *lvl0, int
                      orbhip_keypoint *kps, uint8_t *desc, int32_t *counts, int cap, int B, long long mirror)
 {
     orb_path(ORB_PATH_DESCRIBE);
-    static const int kpwEnv = ORB_TUNE("DESCRIBE_KPW", 0);
-    const int kpw = mirror ? 8 : kpwEnv == 8 || kpwEnv == 16 || kpwEnv == 32 ? kpwEnv : (B >= 8 ? 16 : 8);   // (mirror: single frames only)
-    // workgroup -> (slot block, frame): ORBHIP_DESCRIBE_MAP overrides this kernel's mapping alone (A/B runs)
-    static const int dmap = ORB_TUNE("DESCRIBE_MAP", -1);
-    const int mapArg = dmap >= 0 ? (dmap | (orb_xcd_chunk() << 8)) : orb_xcd_arg(DESCRIBE_DEFAULT_MAP);
+    const int kpw = mirror || B < 8 || !angle_umax_is_31(G) ? 8 : 16;   // (mirror: single frames only)
     static const int phases = ORB_TUNE("DESCRIBE_PHASES", 3);
     (void)phases;
     // occupancy experiment only: unused dynamic LDS caps the workgroups per CU
     static const int padLds = ORB_TUNE("DESCRIBE_PADLDS", 0);
-    const int nblk = (G.totalKps + kpw - 1) / kpw;
-    dim3 grid((mapArg & 255) ? (nblk + 7) / 8 * 8 : nblk, B, 1), block(256, 1, 1);
-    // the one-load form of the angle phase is written for the umax table of a 31-pixel patch (always what orb_init_tables computes)
-    static const int ax4Env = ORB_TUNE("DESCRIBE_AX4", 1);
-    static const int umaxWant[16] = {ANGLE_UMAX_VALUES};
-    bool ax4 = ax4Env != 0 && kpw == 16;
-    for (int v = 0; v < 16; v++) ax4 = ax4 && G.umax[v] == umaxWant[v];
+    dim3 grid(orb_xcd_pad((G.totalKps + kpw - 1) / kpw), B, 1), block(256, 1, 1);   // XCD mode 4
 #define ORB_LAUNCH_DESCRIBE(KERN)                                                                                               \
     hipLaunchKernelGGL(KERN, grid, block, (size_t)padLds, s, G, lvl0, stride0, (unsigned long long)frame0, pyr,                     \
                        (unsigned long long)pyrFrame, blur, (unsigned long long)blurFrame, lvlKp, lvlKpCnt, lvlAngle, kps, desc, \
-                       counts, cap, mapArg, mirror ORB_ABL_ARG(phases))
-    if (kpw == 32)
-        ORB_LAUNCH_DESCRIBE((k_describe<32, false>));
-    else if (kpw == 16 && ax4)
-        ORB_LAUNCH_DESCRIBE((k_describe<16, true>));
-    else if (kpw == 16)
-        ORB_LAUNCH_DESCRIBE((k_describe<16, false>));
+                       counts, cap, 4, mirror ORB_ABL_ARG(phases))
+    if (kpw == 16)
+        ORB_LAUNCH_DESCRIBE((k_describe<16>));
     else if (mirror)
-        ORB_LAUNCH_DESCRIBE((k_describe<8, false, true>));
+        ORB_LAUNCH_DESCRIBE((k_describe<8, true>));
     else
-        ORB_LAUNCH_DESCRIBE((k_describe<8, false>));
+        ORB_LAUNCH_DESCRIBE((k_describe<8>));
 #undef ORB_LAUNCH_DESCRIBE
 }
-

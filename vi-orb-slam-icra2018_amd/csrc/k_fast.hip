@@ -656,11 +656,11 @@ __global__ __launch_bounds__(256, 8) void k_fast(const OrbLevels G, const uint8_
 //     (7-12 % of the entries are such pixels, so practically every wave paid for both polarities of all its 64 entries).
 // Tiles outside these bounds (other cell sizes, ORBHIP_FAST_PITCH=0) run k_fast<0>.
 // =====================================================================================================================
-// workgroup -> (run, frame) of the fixed-layout kernel: 4 = a whole frame's runs on one XCD (grid (8, runs, B / 8), see the kernel).
+// workgroup -> (run, frame) of the fixed-layout kernel from 8 frames up: mode 4 = a whole frame's runs on one XCD (grid (8, runs, B / 8),
+// see the kernel).
 // Measured (r04, gpurun_out/r04_fast2 -> profiles/r04): fabric reads 1.91 -> 0.92 GB per 1024 frames (1.13 x the algorithmic bytes)
 // at the same 1.02 ms -- the kernel is bound by vector and LDS issue, not by its loads; the r01 mappings paid an integer division
 // per thread for the same traffic and were slower.
-#define FAST_DEFAULT_XCD 4
 #ifndef ORB_FAST_TILE_BY_VALUE
 #define ORB_FAST_TILE_BY_VALUE 1
 #endif
@@ -868,7 +868,7 @@ static_assert(ff_max_lds(176, FAST_FIX_ROWS) <= 160 * 1024 / 8, "k_fast_fix<176>
 static_assert(ff_max_lds(160, FAST_FIX_ROWS) <= 160 * 1024 / 8, "k_fast_fix<160>: the eighth workgroup per CU no longer fits");
 static_assert(ff_max_lds(208, FF_RHM_TALL) <= 160 * 1024 / 6, "k_fast_fix<208, tall>: fewer than six workgroups per CU");
 
-template <int PITCH, bool DEFER, int RHM>
+template <int PITCH, int RHM>
 __global__ __launch_bounds__(256, 8) void k_fast_fix(const uint8_t *__restrict__ lvl0, int stride0, unsigned long long frame0,
                                                      const uint8_t *__restrict__ pyr, unsigned long long pyrFrame,
                                                      const FastTile *__restrict__ tiles, uint32_t *__restrict__ cand,
@@ -1069,40 +1069,31 @@ __global__ __launch_bounds__(256, 8) void k_fast_fix(const uint8_t *__restrict__
             if (slot < cornerCap) s_corner[slot] = (uint16_t)ent;
         };
         if (nlist <= listCap) {
-            if (DEFER) {
-                const uint32_t deferCountAddr = (uint32_t)(uintptr_t)&s_deferCount;
-                for (int e = tid; e < nlist; e += 256) {
-                    const int ent = s_list[e];
-                    const int r = ENT_ROW(ent), j = ENT_COL(ent);
-                    bool other;
-                    int s = fast_score_ring<PITCH, true>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t, &other);
-                    if (other) {
-                        // park the entry at the unused end of the work list (slots >= nlist are never read by this loop);
-                        // if the list is full to that point, finish the pixel here
-                        int d;
-                        asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(d) : "v"(deferCountAddr), "v"(1) : "memory");
-                        const int idx = listCap - 1 - d;
-                        if (idx >= nlist) s_list[idx] = (uint16_t)ent;
-                        else s = fast_score_ring_dark<PITCH>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t);
-                    }
-                    if (s > 0) put_corner(ent, r, j, s);
+            const uint32_t deferCountAddr = (uint32_t)(uintptr_t)&s_deferCount;
+            for (int e = tid; e < nlist; e += 256) {
+                const int ent = s_list[e];
+                const int r = ENT_ROW(ent), j = ENT_COL(ent);
+                bool other;
+                int s = fast_score_ring<PITCH, true>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t, &other);
+                if (other) {
+                    // park the entry at the unused end of the work list (slots >= nlist are never read by this loop);
+                    // if the list is full to that point, finish the pixel here
+                    int d;
+                    asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(d) : "v"(deferCountAddr), "v"(1) : "memory");
+                    const int idx = listCap - 1 - d;
+                    if (idx >= nlist) s_list[idx] = (uint16_t)ent;
+                    else s = fast_score_ring_dark<PITCH>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t);
                 }
-                __syncthreads();
-                // the parked entries, dark polarity only (dense lanes again)
-                const int ndefer = min(s_deferCount, listCap - nlist);
-                for (int e = tid; e < ndefer; e += 256) {
-                    const int ent = s_list[listCap - 1 - e];
-                    const int r = ENT_ROW(ent), j = ENT_COL(ent);
-                    const int s = fast_score_ring_dark<PITCH>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t);
-                    if (s > 0) put_corner(ent, r, j, s);
-                }
-            } else {
-                for (int e = tid; e < nlist; e += 256) {
-                    const int ent = s_list[e];
-                    const int r = ENT_ROW(ent), j = ENT_COL(ent);
-                    const int s = fast_score_ring<PITCH, false>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t, nullptr);
-                    if (s > 0) put_corner(ent, r, j, s);
-                }
+                if (s > 0) put_corner(ent, r, j, s);
+            }
+            __syncthreads();
+            // the parked entries, dark polarity only (dense lanes again)
+            const int ndefer = min(s_deferCount, listCap - nlist);
+            for (int e = tid; e < ndefer; e += 256) {
+                const int ent = s_list[listCap - 1 - e];
+                const int r = ENT_ROW(ent), j = ENT_COL(ent);
+                const int s = fast_score_ring_dark<PITCH>(pixAddr + (uint32_t)(__mul24(r, pitch) + (j - 3)), t);
+                if (s > 0) put_corner(ent, r, j, s);
             }
         } else {
             int TWx = TW;
@@ -1338,8 +1329,7 @@ static void launch_fast_levels(hipStream_t s, const OrbLevels &G, const uint8_t 
     static const int forced = ORB_TUNE("FAST_LISTCAP", 0);   // tests force every list to overflow
     static const int phases = ORB_TUNE("FAST_PHASES", 99);
     (void)phases;
-    static const int fastXcd = ORB_TUNE("FAST_XCD", FAST_DEFAULT_XCD);   // workgroup -> (run, frame) of the fixed-layout kernel
-    dim3 grid(orb_xcd_grid(ntiles), B, 1), block(256, 1, 1);
+    dim3 grid(ntiles, B, 1), block(256, 1, 1);
     // r02 kernel: work list = a quarter of the tile's pixels (the first pass runs at iniThFAST), corner list = a sixteenth;
     // bitmap and row prefix per (cell, row).  Tiles that exceed the lists take the exact fallback paths.
     const int px = listBytes / 2;                      // sp * hCell of the largest tile
@@ -1359,39 +1349,30 @@ static void launch_fast_levels(hipStream_t s, const OrbLevels &G, const uint8_t 
     const size_t lds = (size_t)(pixBytes + scoreBytes + lBytes + cBytes + bitsBytes + preBytes);
     // the fixed-layout kernel when every level fits its bounds (ORBHIP_FAST_FIX=0: the generic kernel)
     static const int fixEnv = ORB_SWITCH("FAST_FIX", 1);
-    static const int deferEnv = ORB_TUNE("FAST_DEFER", 1);
     const int maxCells = fast_tile_cells();   // the configured run length bounds every tile's
     if (fixEnv && fixed && maxRh <= FF_RHM_TALL && maxCells <= FF_NCM) {
         const bool tall = maxRh > FF_RHM;
         const int lc = forced > 0 ? std::min(forced, FF_LISTCAP) : listCapFix, cc = forced > 0 ? std::min(forced, FF_CORNERCAP) : cornerCapFix;
         static const int ldsPad = ORB_TUNE("FAST_LDS_PAD", 0);   // occupancy experiments (liborbhip_ablation.so)
         const size_t ldsScore = (size_t)scoreBytes + 16 + 256 + (size_t)ldsPad;   // + a row: nms_survives_fix reads one below the tile
-        const bool perXcd = fastXcd == 4 && B >= 8;   // (a frame or two: the runs over all XCDs)
+        const bool perXcd = B >= 8;   // mode 4 (above k_fast_fix); a frame or two: the runs over all XCDs
         if (perXcd) grid = dim3(8, ntiles, (B + 7) / 8);
         orb_path(ORB_PATH_FAST_FIX | (tall ? ORB_PATH_FAST_TALL : 0u));
-#define ORB_LAUNCH_FIX(P, D, R)                                                                                              \
-    hipLaunchKernelGGL((k_fast_fix<P, D, R>), grid, block, ldsScore, s, lvl0, stride0, (unsigned long long)frame0, pyr,      \
+#define ORB_LAUNCH_FIX(P, R)                                                                                                 \
+    hipLaunchKernelGGL((k_fast_fix<P, R>), grid, block, ldsScore, s, lvl0, stride0, (unsigned long long)frame0, pyr,         \
                        (unsigned long long)pyrFrame, tiles, cand, cellCnt, G.totalCells, G.totalCands, G.iniTh, G.minTh, lc, \
-                       cc, perXcd ? (4 | (B << 8)) : orb_xcd_arg(), ntiles ORB_ABL_ARG(phases))
-#define ORB_LAUNCH_FIX_P(D, R)                             \
+                       cc, perXcd ? (4 | (B << 8)) : 0, ntiles ORB_ABL_ARG(phases))
+#define ORB_LAUNCH_FIX_P(R)                                \
     switch (fixedFix) {                                    \
-    case 160: ORB_LAUNCH_FIX(160, D, R); break;            \
-    case 176: ORB_LAUNCH_FIX(176, D, R); break;            \
-    case 192: ORB_LAUNCH_FIX(192, D, R); break;            \
-    default: ORB_LAUNCH_FIX(208, D, R); break;             \
+    case 160: ORB_LAUNCH_FIX(160, R); break;               \
+    case 176: ORB_LAUNCH_FIX(176, R); break;               \
+    case 192: ORB_LAUNCH_FIX(192, R); break;               \
+    default: ORB_LAUNCH_FIX(208, R); break;                \
     }
-        if (deferEnv) {
-            if (tall) {
-                ORB_LAUNCH_FIX_P(true, FF_RHM_TALL)
-            } else {
-                ORB_LAUNCH_FIX_P(true, FF_RHM)
-            }
+        if (tall) {
+            ORB_LAUNCH_FIX_P(FF_RHM_TALL)
         } else {
-            if (tall) {
-                ORB_LAUNCH_FIX_P(false, FF_RHM_TALL)
-            } else {
-                ORB_LAUNCH_FIX_P(false, FF_RHM)
-            }
+            ORB_LAUNCH_FIX_P(FF_RHM)
         }
 #undef ORB_LAUNCH_FIX_P
 #undef ORB_LAUNCH_FIX
@@ -1400,7 +1381,7 @@ static void launch_fast_levels(hipStream_t s, const OrbLevels &G, const uint8_t 
 #define ORB_LAUNCH_FAST(P)                                                                                                   \
     hipLaunchKernelGGL(k_fast<P>, grid, block, lds, s, G, lvl0, stride0, (unsigned long long)frame0, pyr,                    \
                        (unsigned long long)pyrFrame, tiles, cand, cellCnt, pixBytes, scoreBytes, lBytes, cBytes, bitsBytes,  \
-                       listCap, cornerCap, orb_xcd_arg(), ntiles ORB_ABL_ARG(phases))
+                       listCap, cornerCap, 0, ntiles ORB_ABL_ARG(phases))
     orb_path(ORB_PATH_FAST_GENERIC);
     switch (fixed) {
     case 176: ORB_LAUNCH_FAST(176); break;

@@ -319,8 +319,7 @@ bool resize_fit_plan(const int32_t *xt, const int32_t *yt, int sw, int sh, int d
             const int TH = rpp * npass;
             if (TH > RF_MAXTH) continue;
             const int nty = (dh + TH - 1) / TH;
-            static const int prologue = ORB_TUNE("RESIZE_FIT_P", 100);   // thread-instructions of a workgroup's fixed part / of a pass (70)
-            const long cost = (long)ntx * nty * (prologue + 70 * npass);
+            const long cost = (long)ntx * nty * (100 + 70 * npass);   // thread-instructions of a workgroup's fixed part (100) / of a pass (70)
             if (best >= 0 && cost >= best) continue;
             // the computed windows hold the taps and fit the staging area
             bool ok = true;
@@ -347,11 +346,11 @@ bool resize_fit_plan(const int32_t *xt, const int32_t *yt, int sw, int sh, int d
 void launch_resize_fit(hipStream_t s, const uint8_t *src, int sw, int sh, int sstride, size_t sframe, uint8_t *dst, int dw, int dh,
                        int dstride, size_t dframe, const int32_t *ytab, const int32_t *gtab, const ResizeFit &f, int B)
 {
-    dim3 grid(orb_xcd_grid(f.ntx * f.nty, 1), B, 1), block(256, 1, 1);
+    dim3 grid(orb_xcd_pad(f.ntx * f.nty), B, 1), block(256, 1, 1);   // XCD mode 1 (orbhip_internal.h)
     orb_path(ORB_PATH_RESIZE_FIT);
     hipLaunchKernelGGL(k_resize_fit, grid, block, 0, s, src, sstride, (unsigned long long)sframe, dst, dw, dh, dstride,
                        (unsigned long long)dframe, reinterpret_cast<const int4 *>(ytab), reinterpret_cast<const int4 *>(gtab), sw, sh,
-                       (float)sw / (float)dw, (float)sh / (float)dh, orb_xcd_arg(1), f.ntx, f.nty, f.twg, f.rpp, f.npass, f.rmagic);
+                       (float)sw / (float)dw, (float)sh / (float)dh, 1, f.ntx, f.nty, f.twg, f.rpp, f.npass, f.rmagic);
 }
 
 // Can every tile of the level stage the window that the kernel derives from the scale factors, and does that window
@@ -389,18 +388,18 @@ void launch_resize(hipStream_t s, const uint8_t *src, int sw, int sh, int sstrid
     const int th = B >= 8 ? 32 : 8;
     orb_path(ORB_PATH_RESIZE_TILES);
     const float winx = hint ? (float)sw / (float)dw : 0.f, winy = hint ? (float)sh / (float)dh : 0.f;
-    dim3 grid(orb_xcd_grid(((dw + RZ_TW - 1) / RZ_TW) * ((dh + th - 1) / th), 1), B, 1);
+    dim3 grid(orb_xcd_pad(((dw + RZ_TW - 1) / RZ_TW) * ((dh + th - 1) / th)), B, 1);   // XCD mode 1 (orbhip_internal.h)
     static const int ldsPad = ORB_TUNE("RESIZE_LDS_PAD", 0);   // occupancy experiment (ablation build): unused dynamic LDS per workgroup
     if (th == 32)
         hipLaunchKernelGGL(k_resize<32>, grid, block, (size_t)ldsPad, s, src, sstride, (unsigned long long)sframe, dst, dw, dh, dstride,
                            (unsigned long long)dframe, reinterpret_cast<const int2 *>(xtab),
                            reinterpret_cast<const int4 *>(ytab), reinterpret_cast<const int4 *>(gtab), sw, sh, winx, winy,
-                           orb_xcd_arg(1));
+                           1);
     else
         hipLaunchKernelGGL(k_resize<8>, grid, block, 0, s, src, sstride, (unsigned long long)sframe, dst, dw, dh, dstride,
                            (unsigned long long)dframe, reinterpret_cast<const int2 *>(xtab),
                            reinterpret_cast<const int4 *>(ytab), reinterpret_cast<const int4 *>(gtab), sw, sh, winx, winy,
-                           orb_xcd_arg(1));
+                           1);
 }
 
 // =====================================================================================================================

@@ -297,11 +297,9 @@ void launch_quadtree(hipStream_t s, const OrbLevels &G, const uint32_t *cand, co
     int maxNodes = 0;
     for (int l = 0; l < G.nlevels; l++) maxNodes = std::max(maxNodes, G.lv[l].kpCap);
     const int qtBytes = (int)((qt_shared_bytes(maxNodes) + 15) & ~(size_t)15);
-    // more threads were measured not to shorten the level-0 workgroup (its passes are barrier / LDS-latency chains);
-    // the switch accepts 64..256 (the kernel's launch bound)
-    static const int forced = ORB_TUNE("QT_THREADS", 256);
-    const int nthreads = forced >= 64 && forced <= 256 && forced % 64 == 0 ? forced : 256;
-    dim3 grid(B, G.nlevels, 1), block(nthreads, 1, 1);
+    // 256 threads (the kernel's launch bound): more were measured not to shorten the level-0 workgroup (its passes are barrier /
+    // LDS-latency chains)
+    dim3 grid(B, G.nlevels, 1), block(256, 1, 1);
     static const int phases = ORB_TUNE("QT_PHASES", 0);
     (void)phases;
     const size_t base = quadtree_lds_bytes(G);

@@ -321,10 +321,9 @@ void launch_vocab_transform(hipStream_t s, const OrbVocabDev &V, const uint8_t *
     hipLaunchKernelGGL(k_vocab_transform<E>, dim3((n + (T) - 1) / (T), 1, 1), dim3((T), 1, 1), 0, s, desc, n, V.L - levelsup,       \
                        V.rootFirst, V.rootLast, reinterpret_cast<const uint4 *>(V.desc), reinterpret_cast<const int2 *>(V.erange), \
                        V.eid, V.eword, V.eweight, word_id, weight, node_id, cnt)
-    static const int quad = ORB_TUNE("VOCAB_QUAD", 1);   // (A/B: 0 = thread per descriptor for batches too)
     if (n <= 16384)
         ORB_LAUNCH_VT(true, 64);
-    else if (quad && !cnt)
+    else if (!cnt)
         hipLaunchKernelGGL(k_vocab_transform_quad, dim3((int)(((size_t)n * VT_LPD + 255) / 256), 1, 1), dim3(256, 1, 1), 0, s, desc, n,
                            V.L - levelsup, V.rootFirst, V.rootLast, reinterpret_cast<const uint4 *>(V.desc),
                            reinterpret_cast<const int2 *>(V.erange), V.eid, V.eword, V.eweight, word_id, weight, node_id);

@@ -14,11 +14,13 @@
 
 // ---- environment switches ----
 // The shipped liborbhip.so reads FOUR environment variables, each choosing between two equivalent paths that are both under
-// the parity tests (ORB_SWITCH): ORBHIP_KNN2_MFMA, ORBHIP_FAST_FIX, ORBHIP_NO_GRAPH, ORBHIP_NO_CHAIN.  Everything else -- tuning
-// knobs, the forced-overflow capacities with which the tests reach the fallback paths, occupancy dummies and the timing-ablation
-// stops that make a kernel return early with INVALID results -- is ORB_TUNE: its default, a compile-time constant, in the shipped
-// library, and an environment variable only in liborbhip_ablation.so (-DORBHIP_ABLATION; built for tests/ and tools/, never
-// loaded by the drop-in classes).  A stray variable in a SLAM process can therefore not change what the library computes.
+// the parity tests (ORB_SWITCH): ORBHIP_KNN2_MFMA, ORBHIP_FAST_FIX, ORBHIP_NO_GRAPH, ORBHIP_NO_CHAIN.  Everything else -- path
+// selectors whose other path production also takes on some geometry, the forced-overflow capacities with which the tests reach
+// the fallback paths, occupancy pads and the timing-ablation stops that make a kernel return early with INVALID results -- is
+// ORB_TUNE: its default, a compile-time constant, in the shipped library, and an environment variable only in
+// liborbhip_ablation.so (-DORBHIP_ABLATION; built for tests/ and tools/, never loaded by the drop-in classes).  A stray variable
+// in a SLAM process can therefore not change what the library computes.  orbhip/capi.py's TUNE_KNOBS lists every ORB_TUNE name
+// (tests/test_shipped_switches.py checks it against these sources).
 #include <stdlib.h>
 static inline int orb_env_int(const char *name, int dflt)
 {
@@ -395,37 +397,16 @@ void launch_bow_match(hipStream_t s, const uint8_t *desc1, const uint8_t *valid1
                       const int32_t *off2, const int32_t *idx2, const int32_t *pairs, int npairs,
                       int th, int th_mode, float nnratio, int32_t *match12, int32_t *match21);
 
-// XCD-aware work assignment for (tile, frame) grids -- a per-kernel default (see orb_xcd_map), off for k_fast.  Workgroups are dealt
-// round-robin over the 8 XCDs by linear id (MI355X_MICROARCH.md, "Workgroup dispatch"; placement affects speed
-// only).  With ORBHIP_XCD_MAP != 0 the grid's x extent is padded to a multiple of 8, workgroup x of a frame runs
-// on XCD x % 8 and takes a tile from a contiguous eighth of the frame's tiles, so the 128-byte lines that
-// neighbouring tiles share (halo rows, row segments straddling a line) are fetched into one XCD's L2 once
-// instead of once per XCD.  Measured (profiles/r01e_xcd_map.md): fabric read traffic of k_fast / k_blur /
-// k_describe falls 2-3x to about the algorithmic bytes, but every variant is SLOWER than the plain mapping
-// (k_fast +2..+100 %): the re-reads are served by the Infinity Cache, the kernels are VALU/LDS- or
-// latency-bound, and spreading neighbouring tiles over all eight L2s balances the load better.  Hence 0.
-static inline int orb_xcd_map(int dflt = 0)
-{
-    static int v = -2;
-    if (v == -2) v = ORB_TUNE("XCD_MAP", -1);
-    return v >= 0 ? v : dflt;   // per-kernel defaults: k_blur 2 (uniform tiles), k_describe / k_resize 1, k_fast 0
-}
-static inline int orb_xcd_chunk();
-static inline int orb_xcd_arg(int dflt = 0);
-static inline int orb_xcd_chunk()
-{
-    static int v = -1;
-    if (v < 0) v = ORB_TUNE("XCD_CHUNK", 4);
-    return v;
-}
-static inline int orb_xcd_grid(int ntiles, int dflt = 0)
-{
-    const int m = orb_xcd_map(dflt);
-    if (!m) return ntiles;
-    const int unit = m == 3 ? 8 * orb_xcd_chunk() : 8;
-    return (ntiles + unit - 1) / unit * unit;
-}
-static inline int orb_xcd_arg(int dflt) { return orb_xcd_map(dflt) | (orb_xcd_chunk() << 8); }
+// XCD-aware work assignment for (tile, frame) grids: the mode, a kernel argument, is fixed per kernel -- k_blur 2, k_resize 1,
+// k_describe / k_describe_blur 4, k_fast 0, k_fast_fix 4 from 8 frames up.  Workgroups are dealt round-robin over the 8 XCDs by
+// linear id (MI355X_MICROARCH.md, "Workgroup dispatch"; placement affects speed only).  Outside k_fast_fix the grid's x extent is
+// then padded to a multiple of 8 (orb_xcd_pad) for every mode but 0; with modes 1 and 2 workgroup x of a frame runs on XCD x % 8
+// and takes a tile from a contiguous eighth of the frame's tiles, so the 128-byte lines that neighbouring tiles share (halo rows, row segments straddling a line) are fetched into one XCD's
+// L2 once instead of once per XCD.  Measured (profiles/r01e_xcd_map.md): fabric read traffic of k_fast / k_blur / k_describe falls
+// 2-3x to about the algorithmic bytes, but every variant is SLOWER than the plain mapping for k_fast (+2..+100 %): the re-reads
+// are served by the Infinity Cache, the kernel is VALU/LDS- or latency-bound, and spreading neighbouring tiles over all eight L2s
+// balances the load better.  Hence 0 for k_fast.
+static inline int orb_xcd_pad(int ntiles) { return (ntiles + 7) / 8 * 8; }
 #ifdef __HIPCC__
 // Minimum over the 16 lanes of a DPP row (result in every lane of the row) / over the wave (a scalar).  The row steps are
 // v_min_i32 with a DPP source operand: the builtin form (min(v, update_dpp(v, v, ...))) compiles to v_mov_b32 + s_nop + v_mov_b32_dpp
@@ -473,17 +454,13 @@ __device__ __forceinline__ void xcd_frame_tile(int nframes, int &tile, int &fram
     }
 }
 // mode 1: band (x % 8 + frame) % 8 -- every XCD sees every band over 8 consecutive frames (tile cost differs
-// between pyramid levels); mode 2: band x % 8; mode 3: chunks of xcdMap >> 8 tiles dealt round-robin.
+// between pyramid levels); mode 2: band x % 8.  The mode is the argument's low byte (k_fast_fix keeps the batch size above it).
 __device__ __forceinline__ int xcd_tile(int xcdMap)
 {
     const unsigned x = blockIdx.x, k = x & 7u, s = x >> 3, bw = gridDim.x >> 3;
     const int mode = xcdMap & 255;
     if (mode == 1) return (int)(((k + blockIdx.y) & 7u) * bw + s);
     if (mode == 2) return (int)(k * bw + s);
-    if (mode == 3) {
-        const unsigned c = (unsigned)xcdMap >> 8;
-        return (int)(((s / c) * 8u + k) * c + s % c);
-    }
     return (int)x;
 }
 #endif

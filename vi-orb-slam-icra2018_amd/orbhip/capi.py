@@ -16,11 +16,9 @@ CSRC = os.path.normpath(os.path.join(_HERE, "..", "csrc"))
 # what the C++ drop-in classes link -- loads the ablation build when one of those knobs is set in the environment (or with
 # ORBHIP_ABLATION=1), so that tests/ and tools/ reach the fallback paths; otherwise the product library.
 TUNE_KNOBS = (
-    "COPY_OUT", "BOW_THREADS", "BOW_GLOBAL_DESC", "BOW_PHASES", "CHAIN_DEPTH", "DESCRIBE_KPW",
-    "DESCRIBE_MAP", "DESCRIBE_PHASES", "DESCRIBE_PADLDS", "DESCRIBE_AX4", "PROJ_SEQ", "PROJ_ROUNDS", "PROJ_K", "INIT_K",
-    "QT_THREADS", "QT_PHASES", "QT_LDSPTS", "QT_THREADS_SMALL", "SETS_COPY", "STEREO_ENT_PER_KP", "FAST_TILE_CELLS", "FAST_LISTCAP",
-    "FAST_PHASES", "FAST_PITCH", "FAST_DEFER", "FAST_LDS_PAD", "XCD_MAP", "XCD_CHUNK", "FAST_XCD", "FRAME_SPLIT", "INIT_STOP",
-    "VOCAB_QUAD", "RESIZE_FIT_P", "RESIZE_FIT", "RESIZE_LDS_PAD", "DESCRIBE_FUSED", "BOW_LANE", "DEBUG_DESTROY",
+    "BOW_GLOBAL_DESC", "BOW_LANE", "BOW_PHASES", "CHAIN_DEPTH", "DESCRIBE_FUSED", "DESCRIBE_PADLDS", "DESCRIBE_PHASES",
+    "FAST_LDS_PAD", "FAST_LISTCAP", "FAST_PHASES", "FAST_PITCH", "FAST_TILE_CELLS", "INIT_K", "INIT_STOP", "PROJ_K", "PROJ_ROUNDS",
+    "PROJ_SEQ", "QT_LDSPTS", "QT_PHASES", "QT_THREADS_SMALL", "RESIZE_FIT", "RESIZE_LDS_PAD", "STEREO_ENT_PER_KP",
 )
 
 

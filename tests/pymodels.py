@@ -257,3 +257,142 @@ def search_by_bow(desc1, valid1, angle1, fv1, desc2, valid2, angle2, fv2, th, st
                 m12[a] = -1
                 nm -= 1
     return nm, m12, m21
+
+
+# ---- Frame::ComputeStereoMatches (src/Frame.cc:810-984), restated from the reference ----
+STEREO_BRANCHES = ("band_empty", "octave_rejected", "no_candidate_under_75", "border_skip", "bestinc_at_edge",
+                   "deltaR_out", "disparity_out", "disparity_zero", "median_cut", "kept", "median_above_255")
+
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
+
+
+def _roundf(v):
+    """C++ round(float): halves away from zero (np.round would round them to even)."""
+    v = np.float32(v)
+    r = np.floor(np.abs(v))
+    if np.abs(v) - r >= np.float32(0.5):
+        r += np.float32(1)
+    return np.float32(np.copysign(r, v))
+
+
+def stereo_matches(pyrL, pyrR, kL, dL, kR, dR, scale_factors, inv_scale_factors, mb, mbf):
+    """pyrL / pyrR: lists of pyramid levels (uint8 2-D); kL / kR: keypoint records (x, y, octave); dL / dR: [n, 32] uint8.
+    float32 throughout, in the reference's operation order.  Returns (mvuRight, mvDepth, n_before_cut, counters): one
+    outcome counter per left keypoint (band_empty / no_candidate_under_75 / border_skip / bestinc_at_edge / deltaR_out /
+    disparity_out / median_cut / kept), plus disparity_zero (accepted with disparity == 0), octave_rejected (candidate pairs
+    dropped by the +-1 octave rule) and median_above_255 (1 when the median patch distance exceeds one byte).
+    Where the reference is undefined (a band row outside the image, an empty match set) the model does what the oracle
+    documents; a patch read outside the image raises instead of wrapping around."""
+    f32 = np.float32
+    cnt = dict.fromkeys(STEREO_BRANCHES, 0)
+    sf = [f32(s) for s in scale_factors]
+    isf = [f32(s) for s in inv_scale_factors]
+    nL, nR = len(kL), len(kR)
+    uRight = np.full(nL, -1.0, np.float32)
+    depth = np.full(nL, -1.0, np.float32)
+    nRows = pyrL[0].shape[0]
+    rows = [[] for _ in range(nRows)]                          # vRowIndices, :822-836 (ascending iR in every row)
+    for iR in range(nR):
+        kpY = f32(kR["y"][iR])
+        r = f32(2.0) * sf[int(kR["octave"][iR])]
+        maxr, minr = int(np.ceil(kpY + r)), int(np.floor(kpY - r))
+        for yi in range(minr, maxr + 1):
+            if 0 <= yi < nRows:
+                rows[yi].append(iR)
+    minZ = f32(mb)
+    minD = f32(0)
+    maxD = f32(mbf) / minZ
+    xR = kR["x"].astype(np.float32)
+    octR = kR["octave"].astype(np.int64)
+    dR = np.asarray(dR, np.uint8).reshape(-1, 32)
+    dL = np.asarray(dL, np.uint8).reshape(-1, 32)
+    vDistIdx = []
+    w = L = 5
+    for iL in range(nL):
+        levelL = int(kL["octave"][iL])
+        vL, uL = f32(kL["y"][iL]), f32(kL["x"][iL])
+        row = int(vL)                                          # vRowIndices[vL]: float -> size_t truncates
+        cand = rows[row] if 0 <= row < nRows else []
+        if not cand:
+            cnt["band_empty"] += 1
+            continue
+        minU, maxU = uL - maxD, uL - minD
+        if maxU < 0:
+            cnt["band_empty"] += 1
+            continue
+        cand = np.array(cand, np.int64)
+        octok = (octR[cand] >= levelL - 1) & (octR[cand] <= levelL + 1)
+        cnt["octave_rejected"] += int((~octok).sum())
+        cand = cand[octok]
+        cand = cand[(xR[cand] >= minU) & (xR[cand] <= maxU)]
+        bestDist, bestIdxR = 100, 0                            # TH_HIGH
+        if len(cand):
+            dist = _POP8[dL[iL][None, :] ^ dR[cand]].sum(axis=1)
+            j = int(np.argmin(dist))                           # first minimum in ascending iR = the strict '<' scan
+            if dist[j] < bestDist:
+                bestDist, bestIdxR = int(dist[j]), int(cand[j])
+        if not bestDist < (100 + 50) // 2:
+            cnt["no_candidate_under_75"] += 1
+            continue
+        uR0 = xR[bestIdxR]
+        scaleFactor = isf[levelL]
+        scaleduL = _roundf(uL * scaleFactor)
+        scaledvL = _roundf(vL * scaleFactor)
+        scaleduR0 = _roundf(uR0 * scaleFactor)
+        imL, imR = pyrL[levelL], pyrR[levelL]
+        iniu = scaleduR0 + f32(L - w)
+        endu = scaleduR0 + f32(L + w + 1)
+        if iniu < 0 or endu >= imR.shape[1]:
+            cnt["border_skip"] += 1
+            continue
+        cy, cxL, cxR = int(scaledvL), int(scaleduL), int(scaleduR0)
+        if not (cy - w >= 0 and cy + w < imL.shape[0] and cxL - w >= 0 and cxL + w < imL.shape[1] and cxR - L - w >= 0
+                and cxR + L + w < imR.shape[1]):
+            raise ValueError("stereo model: the patches of left keypoint %d leave the image (undefined in the reference)" % iL)
+        IL = imL[cy - w:cy + w + 1, cxL - w:cxL + w + 1].astype(np.float32)
+        IL = IL - IL[w, w]
+        bestSad, bestincR = 2147483647, 0
+        vDists = np.zeros(2 * L + 1, np.float32)
+        for incR in range(-L, L + 1):
+            IR = imR[cy - w:cy + w + 1, cxR + incR - w:cxR + incR + w + 1].astype(np.float32)
+            IR = IR - IR[w, w]
+            d = f32(np.abs(IL.astype(np.float64) - IR).sum())  # cv::norm(NORM_L1) in double, stored in a float
+            if d < f32(bestSad):
+                bestSad = int(d)
+                bestincR = incR
+            vDists[L + incR] = d
+        if bestincR == -L or bestincR == L:
+            cnt["bestinc_at_edge"] += 1
+            continue
+        dist1, dist2, dist3 = vDists[L + bestincR - 1], vDists[L + bestincR], vDists[L + bestincR + 1]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            deltaR = (dist1 - dist3) / (f32(2.0) * (dist1 + dist3 - f32(2.0) * dist2))
+        if deltaR < -1 or deltaR > 1:
+            cnt["deltaR_out"] += 1
+            continue
+        bestuR = sf[levelL] * (f32(scaleduR0) + f32(bestincR) + deltaR)
+        disparity = uL - bestuR
+        if disparity >= minD and disparity < maxD:
+            if disparity <= 0:
+                cnt["disparity_zero"] += 1
+                disparity = f32(0.01)
+                bestuR = f32(np.float64(uL) - 0.01)            # `uL-0.01` is a double expression, :957
+            depth[iL] = f32(mbf) / disparity
+            uRight[iL] = bestuR
+            vDistIdx.append((bestSad, iL))
+        else:
+            cnt["disparity_out"] += 1
+    n = len(vDistIdx)
+    if n:
+        vDistIdx.sort()
+        median = f32(vDistIdx[n // 2][0])
+        thDist = f32(1.5) * f32(1.4) * median
+        cnt["median_above_255"] += int(vDistIdx[n // 2][0] > 255)
+        for i in range(n - 1, -1, -1):
+            if f32(vDistIdx[i][0]) < thDist:
+                break
+            uRight[vDistIdx[i][1]] = -1
+            depth[vDistIdx[i][1]] = -1
+            cnt["median_cut"] += 1
+    cnt["kept"] = n - cnt["median_cut"]
+    return uRight, depth, n, cnt

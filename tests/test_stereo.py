@@ -126,3 +126,388 @@ def test_hip_stereo_row_bin_overflow_falls_back_exactly(oracle, tmp_path):
     kR, dR = oR(R)
     ru, rz, rn = oracle.stereo_matches(oL, kL, dL, oR, kR, dR, 0.2, 40.0)
     assert int(got["n"]) == rn and got["u"].tobytes() == ru.tobytes() and got["z"].tobytes() == rz.tobytes() and rn > 200
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# Against an independent model (tests/pymodels.py, restated from src/Frame.cc:810-984) on resampled and planted scenes
+# (tests/stereo_scenes.py).  The GPU tests compare the kernels with the oracle bit for bit, so the model is what ties both
+# to the reference: a misreading the oracle and the kernels shared would pass every GPU test.
+# ------------------------------------------------------------------------------------------------------------------------
+def _model(oL, oR, kL, dL, kR, dR, mb, mbf):
+    import pymodels
+    P = oL.params
+    return pymodels.stereo_matches([oL.pyramid(l) for l in range(oL.nlevels)], [oR.pyramid(l) for l in range(oR.nlevels)],
+                                   kL, dL, kR, dR, list(P.mvScaleFactor)[:oL.nlevels],
+                                   list(P.mvInvScaleFactor)[:oL.nlevels], mb, mbf)
+
+
+def _same(a, b):
+    return a.tobytes() == b.tobytes()
+
+
+def _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, mb, mbf, what):
+    """oracle.stereo_matches, checked bit for bit against the model; returns (u, z, n, model counters)."""
+    ru, rz, rn = oracle.stereo_matches(oL, kL, dL, oR, kR, dR, mb, mbf)
+    mu, mz, mn, cnt = _model(oL, oR, kL, dL, kR, dR, mb, mbf)
+    bad = np.nonzero((ru.view(np.uint32) != mu.view(np.uint32)) | (rz.view(np.uint32) != mz.view(np.uint32)))[0][:5]
+    assert len(bad) == 0, "%s: oracle and model differ at %s: u %s / %s, z %s / %s" % (what, bad, ru[bad], mu[bad], rz[bad],
+                                                                                     mz[bad])
+    assert rn == mn, "%s: n_before_cut oracle %d, model %d" % (what, rn, mn)
+    return ru, rz, rn, cnt
+
+
+def _add(total, cnt):
+    for k, v in cnt.items():
+        total[k] = total.get(k, 0) + v
+
+
+def _natural(oracle, kind, seed, W, H, nf, mb, mbf):
+    """A natural scene of `kind` through the oracle: (extractors, planted keypoints and descriptors, mb, mbf, images)."""
+    import stereo_scenes as ss
+    left, right, plants, mb, mbf = ss.scene(kind, seed, W, H, mb, mbf)
+    oL, oR = oracle.Extractor(nf), oracle.Extractor(nf)
+    kL, dL = oL(left)
+    kR, dR = oR(right)
+    return oL, oR, ss.plant_zero(kL, dL, kR, dR, plants, seed), mb, mbf, (left, right)
+
+
+# Branch counters every scene set below must reach.  deltaR_out is unreachable: bestincR is the first strict minimum,
+# so dist1 > dist2 <= dist3 and |deltaR| = |dist1 - dist3| / (2 (dist1 + dist3 - 2 dist2)) <= 1/2 (:938-946); the
+# model still counts it, and it must stay 0.  border_skip is unreachable for extractor-like keypoints
+# (tests/stereo_scenes.py), so only the CPU set, which plants at the border, has to reach it.
+_REACHABLE = ("band_empty", "octave_rejected", "no_candidate_under_75", "bestinc_at_edge", "disparity_out",
+              "disparity_zero", "median_cut", "kept", "median_above_255")
+
+
+def _assert_coverage(total, extra=()):
+    missing = [k for k in _REACHABLE + tuple(extra) if total.get(k, 0) == 0]
+    assert not missing, "stereo branches never reached: %s (%s)" % (missing, total)
+    assert total.get("deltaR_out", 0) == 0, total
+
+
+def _planted_cases():
+    """The known-answer pairs: (name, Planted, expected n_before_cut or None).  The comment at each names the one-line
+    misreading it catches, in the oracle, the model or the kernels."""
+    from stereo_scenes import Planted
+    f32 = np.float32
+    out = []
+    # u in [uL - maxD, uL], both ends inclusive (:850-851, :875): `uR <= maxU` -> `<` loses the third pair
+    p = Planted(11)
+    px = p.slots[0][0]
+    p.pair(D=23, right=[(px - 24, 0, 5)])                                                 # uR == minU (maxD = 24)
+    px = p.slots[0][0]
+    p.pair(D=23, right=[(np.nextafter(f32(px - 24), f32(-1e9)), 0, 5)], keep=False)       # one float step below
+    px = p.slots[0][0]
+    p.pair(D=1, right=[(px, 0, 5)])                                                       # uR == maxU == uL
+    px = p.slots[0][0]
+    p.pair(D=1, right=[(np.nextafter(f32(px), f32(1e9)), 0, 5)], keep=False)              # one float step above
+    out.append(("bounds", p, 2))
+    # right octave within levelL +- 1 (:869-870): octave levelL + 2 is ignored even at distance 0
+    p = Planted(12)
+    px = p.slots[0][0]
+    p.pair(D=3, right=[(px - 3, 2, 0)], keep=False)
+    px = p.slots[0][0]
+    p.pair(D=3, right=[(px - 3, 1, 0)])
+    out.append(("octave", p, 1))
+    # equal Hamming distances: the lower right index wins (strict '<' over the row list in ascending iR, :879)
+    p = Planted(13)
+    px = p.slots[0][0]
+    p.pair(D=3, right=[(px - 3, 0, 5), (px - 20, 0, 5)])
+    px = p.slots[0][0]
+    p.pair(D=3, right=[(px - 20, 0, 5), (px - 3, 0, 5)], keep=None)
+    out.append(("ties", p, None))
+    # bestDist < thOrbDist = 75 (:887): `dist < thOrbDist` -> `<=` matches the 75
+    p = Planted(14)
+    px = p.slots[0][0]
+    p.pair(D=4, right=[(px - 4, 0, 74)])
+    px = p.slots[0][0]
+    p.pair(D=4, right=[(px - 4, 0, 75)], keep=False)
+    out.append(("th75", p, 1))
+    # disparity exactly 0 (:955-958): 0.01, and uL - 0.01 in double; without the substitution u = uL and the depth is inf
+    p = Planted(15)
+    p.pair(D=0)
+    p.pair(D=0, sad=60)
+    p.pair(D=2, sad=55)
+    out.append(("disparity0", p, 3))
+    # the median cut (:970-983) removes distances >= 1.5f*1.4f*median.  Median 130 gives thDist = 273.0 exactly, so
+    # `>=` -> `>` keeps the 273; the distances pass 255, the upper byte of k_stereo_cut's two-level select
+    p = Planted(16)
+    for s in (130, 273, 130, 272, 130):
+        p.pair(D=5, sad=s, keep=s != 273)
+    out.append(("cut273", p, 5))
+    # n_before_cut of 1, 2 and 4: the median is element n/2 of the sorted list ([20, 42]: element 0 would cut the 42;
+    # [10, 10, 21, 30]: element 1 would cut 21 and 30); a lone distance of 0 has thDist = 0 and is cut
+    p = Planted(17)
+    p.pair(D=6, sad=50)
+    p.lonely(300, 400)                      # and a left keypoint with an empty row band
+    out.append(("n1", p, 1))
+    p = Planted(18)
+    p.pair(D=6, sad=0, keep=False)
+    out.append(("n1_sad0", p, 1))
+    p = Planted(19)
+    p.pair(D=6, sad=42)
+    p.pair(D=7, sad=20)
+    out.append(("n2", p, 2))
+    p = Planted(20)
+    for s in (21, 10, 30, 10):
+        p.pair(D=2, sad=s)
+    out.append(("n4", p, 4))
+    return out
+
+
+def _check_want(what, p, u, z, n, n_want):
+    wu, wz = p.want()
+    fixed = ~np.isnan(wu)
+    assert _same(u[fixed], wu[fixed]) and _same(z[fixed], wz[fixed]), "%s: u %s z %s, want u %s z %s" % (what, u, z, wu, wz)
+    free = ~fixed
+    assert (u[free] != p.avoid()[free]).all(), "%s: u %s must not be %s" % (what, u, p.avoid())
+    assert n_want is None or n == n_want, "%s: n_before_cut %d, want %d" % (what, n, n_want)
+
+
+def _oracle_pair(oracle, p):
+    oL, oR = oracle.Extractor(500), oracle.Extractor(500)
+    oL(p.left)
+    oR(p.right)
+    return oL, oR
+
+
+@pytest.mark.parametrize("kind", ["shift", "slant04", "slant13", "slant25", "gain", "maxd", "photo"])
+def test_oracle_matches_model_on_scene_kinds(oracle, kind):
+    import stereo_scenes as ss
+    if kind not in ss.kinds():
+        pytest.skip("no sample photographs in this image")
+    W, H, _, mb, mbf = ss.EUROC
+    oL, oR, (kL, dL, kR, dR), mb, mbf, _ = _natural(oracle, kind, 3, W, H, 1000, mb, mbf)
+    u, z, n, cnt = _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, mb, mbf, kind)
+    assert n > 100 and (u >= 0).sum() > 50, (kind, n, cnt)
+    assert cnt["disparity_zero"] >= 2, (kind, cnt)                 # the planted mirror patches
+    # degenerate sizes on the same pyramids: no right keypoints, one left keypoint, one right keypoint
+    u0, _, n0, c0 = _oracle_and_model(oracle, oL, oR, kL, dL, kR[:0], dR[:0], mb, mbf, kind + "/nR=0")
+    assert n0 == 0 and (u0 == -1).all() and c0["band_empty"] == len(kL)
+    for i in (0, len(kL) - 1, int(np.argmax(u >= 0))):
+        _oracle_and_model(oracle, oL, oR, kL[i:i + 1], dL[i:i + 1], kR, dR, mb, mbf, kind + "/nL=1 #%d" % i)
+    _oracle_and_model(oracle, oL, oR, kL, dL, kR[-1:], dR[-1:], mb, mbf, kind + "/nR=1")
+
+
+def test_oracle_and_model_reach_every_stereo_branch(oracle):
+    """The CPU scene set reaches every branch, the border skip included (planted only at the right edge and with
+    scaleduR0 < 0; tests/stereo_scenes.py)."""
+    import stereo_scenes as ss
+    from stereo_scenes import Planted
+    total = {}
+    W, H, _, mb, mbf = ss.EUROC
+    for kind in ("gain", "maxd", "slant25"):
+        oL, oR, (kL, dL, kR, dR), kmb, kmbf, _ = _natural(oracle, kind, 5, W, H, 1000, mb, mbf)
+        _add(total, _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, kmb, kmbf, kind)[3])
+    p = Planted(21)
+    p.pair(D=2)
+    W = Planted.W
+    p.lonely(W - 8, 300, xr=W - 9)          # right edge: endu = W - 9 + 11 >= W; the left patch still fits
+    p.lonely(6, 340, xr=-0.6)               # round(-0.6) = -1: iniu < 0; the left patch starts at column 1
+    p.lonely(300, 400)                      # no right keypoint in its band
+    oL, oR = _oracle_pair(oracle, p)
+    kL, dL, kR, dR = p.arrays()
+    u, z, n, cnt = _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, p.mb, p.mbf, "border")
+    _check_want("border", p, u, z, n, 1)
+    assert cnt["border_skip"] == 2 and cnt["band_empty"] == 1, cnt
+    _add(total, cnt)
+    for name, p, _ in _planted_cases():
+        oL, oR = _oracle_pair(oracle, p)
+        _add(total, _oracle_and_model(oracle, oL, oR, *p.arrays(), p.mb, p.mbf, name)[3])
+    _assert_coverage(total, ("border_skip",))
+
+
+@pytest.mark.parametrize("case", ["bounds", "octave", "ties", "th75", "disparity0", "cut273", "n1", "n1_sad0", "n2", "n4"])
+def test_stereo_known_answers_oracle_and_model(oracle, case):
+    name, p, n_want = [c for c in _planted_cases() if c[0] == case][0]
+    oL, oR = _oracle_pair(oracle, p)
+    kL, dL, kR, dR = p.arrays()
+    ru, rz, rn = oracle.stereo_matches(oL, kL, dL, oR, kR, dR, p.mb, p.mbf)
+    _check_want(name + " (oracle)", p, ru, rz, rn, n_want)
+    mu, mz, mn, _ = _model(oL, oR, kL, dL, kR, dR, p.mb, p.mbf)
+    _check_want(name + " (model)", p, mu, mz, mn, n_want)
+
+
+def _tally_branches(tally, cnt):
+    for k, v in cnt.items():
+        tally("stereo " + k, v)
+
+
+@pytest.mark.gpu
+def test_hip_stereo_scene_kinds_and_known_answers(oracle, tally):
+    """ComputeStereoMatches equals the oracle bit for bit, and the oracle equals the model, on every scene kind at KITTI
+    and EuRoC sizes (natural keypoints plus planted disparity-0 pairs) and on the known-answer pairs, whose answers are
+    checked too.  The model's branch counters over all of them go to the terminal summary and must cover every
+    reachable branch."""
+    import stereo_scenes as ss
+    from orbhip.extractor import ComputeStereoMatches, ORBextractor
+    total = {}
+
+    def run(exL, exR, oL, oR, left, right, arrays, mb, mbf, what):
+        kL, dL = exL(left)
+        kR, dR = exR(right)
+        rkL, _ = oL(left)
+        rkR, _ = oR(right)
+        assert kL.tobytes() == rkL.tobytes() and kR.tobytes() == rkR.tobytes(), what
+        kL, dL, kR, dR = arrays(kL, dL, kR, dR)
+        ru, rz, rn, cnt = _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, mb, mbf, what)
+        u, z, n = ComputeStereoMatches(exL, kL, dL, exR, kR, dR, mb, mbf)
+        bad = np.nonzero((u.view(np.uint32) != ru.view(np.uint32)) | (z.view(np.uint32) != rz.view(np.uint32)))[0][:5]
+        assert len(bad) == 0 and n == rn, "%s: HIP and oracle differ at %s: u %s / %s, z %s / %s, n %d / %d" % (
+            what, bad, u[bad], ru[bad], z[bad], rz[bad], n, rn)
+        _add(total, cnt)
+        return u, z, n
+
+    for si, (W, H, nf, mb, mbf) in enumerate((ss.KITTI, ss.EUROC)):
+        exL, exR = ORBextractor(nf, max_w=W, max_h=H), ORBextractor(nf, max_w=W, max_h=H)
+        oL, oR = oracle.Extractor(nf), oracle.Extractor(nf)
+        for ki, kind in enumerate(ss.kinds()):
+            seed = 40 + 10 * si + ki
+            left, right, plants, kmb, kmbf = ss.scene(kind, seed, W, H, mb, mbf)
+            what = "%s %dx%d seed %d" % (kind, W, H, seed)
+            u, _, n = run(exL, exR, oL, oR, left, right, lambda *a: ss.plant_zero(*a, plants, seed), kmb, kmbf, what)
+            assert n > 100 and (u >= 0).sum() > 50, what
+        exL.close()
+        exR.close()
+    W, H = ss.Planted.W, ss.Planted.H
+    exL, exR = ORBextractor(500, max_w=W, max_h=H), ORBextractor(500, max_w=W, max_h=H)
+    oL, oR = oracle.Extractor(500), oracle.Extractor(500)
+    for name, p, n_want in _planted_cases():
+        u, z, n = run(exL, exR, oL, oR, p.left, p.right, lambda *a: p.arrays(), p.mb, p.mbf, name)
+        _check_want(name + " (HIP)", p, u, z, n, n_want)
+    exL.close()
+    exR.close()
+    _tally_branches(tally, total)
+    _assert_coverage(total)
+
+
+def _batch_case():
+    """B = 8 EuRoC-size pairs of mixed kinds with ragged counts: pair 1 has no left keypoints, pair 2 no right ones,
+    pairs 3 and 4 keep only some; every other pair gets the planted disparity-0 keypoints."""
+    import stereo_scenes as ss
+    W, H, nf, mb, mbf = ss.EUROC
+    kinds = ss.kinds()
+    scenes = [ss.scene(kinds[b % len(kinds)], 70 + b, W, H, mb, mbf) for b in range(8)]
+    limits = [(None, None), (0, None), (None, 0), (300, None), (None, 200), (None, None), (None, None), (None, None)]
+    return scenes, limits
+
+
+def _batch_arrays(kL, dL, kR, dR, plants, limit, seed):
+    import stereo_scenes as ss
+    if limit[0] == 0 or limit[1] == 0:
+        plants = []
+    kL, dL, kR, dR = ss.plant_zero(kL[:limit[0]], dL[:limit[0]], kR[:limit[1]], dR[:limit[1]], plants, seed)
+    return kL, dL, kR, dR
+
+
+@pytest.mark.gpu
+def test_hip_stereo_batched_device_mixed_and_ragged(oracle, tally):
+    """orbhip_stereo_match_device on B = 8 pairs of mixed scene kinds with ragged counts (nL = 0, nR = 0, truncated),
+    every pair and d_nmatch against the oracle, and the oracle against the model.  The pairs share one call, so one
+    mixed mb / mbf is used for all of them (the "maxd" kind's baseline does not apply here)."""
+    import hiprt
+    import stereo_scenes as ss
+    from orbhip.capi import check
+    from orbhip.extractor import ORBextractor
+    scenes, limits = _batch_case()
+    B = len(scenes)
+    W, H, nf, mb, mbf = ss.EUROC
+    exL, exR = ORBextractor(nf, max_w=W, max_h=H, max_batch=B), ORBextractor(nf, max_w=W, max_h=H, max_batch=B)
+    cap, stride = exL.cap, 768
+    raw = {}
+    for side, ex, col in (("L", exL, 0), ("R", exR, 1)):
+        host = np.zeros((B, H, stride), np.uint8)
+        host[:, :, :W] = np.stack([s[col] for s in scenes])
+        d_img = hiprt.DevBuf.from_numpy(host)
+        d_k, d_d, d_c = hiprt.DevBuf(B * cap * 28), hiprt.DevBuf(B * cap * 32), hiprt.DevBuf(B * 4)
+        ex.extract_batch_device(d_img.ptr, B, W, H, stride, H * stride, d_k.ptr, d_d.ptr, cap, d_c.ptr)
+        raw[side] = (d_img, d_k.to_numpy(oracle.KP_DTYPE, (B, cap)), d_d.to_numpy(np.uint8, (B, cap, 32)),
+                     d_c.to_numpy(np.int32, (B,)))
+        for x in (d_k, d_d, d_c):
+            x.free()
+    # the planted / truncated keypoint sets, uploaded in the layout extract_batch_device writes
+    sets = []
+    kps = {s: np.zeros((B, cap), oracle.KP_DTYPE) for s in "LR"}
+    desc = {s: np.zeros((B, cap, 32), np.uint8) for s in "LR"}
+    cnt = {s: np.zeros(B, np.int32) for s in "LR"}
+    for b in range(B):
+        _, kL, dL, cL = raw["L"]
+        _, kR, dR, cR = raw["R"]
+        a = _batch_arrays(kL[b, :cL[b]], dL[b, :cL[b]], kR[b, :cR[b]], dR[b, :cR[b]], scenes[b][2], limits[b], 70 + b)
+        sets.append(a)
+        for s, k, d in (("L", a[0], a[1]), ("R", a[2], a[3])):
+            assert len(k) <= cap
+            kps[s][b, :len(k)], desc[s][b, :len(k)], cnt[s][b] = k, d, len(k)
+    dev = [hiprt.DevBuf.from_numpy(x) for x in (kps["L"], desc["L"], cnt["L"], kps["R"], desc["R"], cnt["R"])]
+    d_u, d_z, d_n = hiprt.DevBuf(B * cap * 4), hiprt.DevBuf(B * cap * 4), hiprt.DevBuf(B * 4)
+    check(exL._L.orbhip_stereo_match_device(exL.handle, exR.handle, *[x.ptr for x in dev], cap, B, mb, mbf, d_u.ptr,
+                                            d_z.ptr, d_n.ptr), exL.handle, "orbhip_stereo_match_device")
+    exL.sync()
+    u = d_u.to_numpy(np.float32, (B, cap))
+    z = d_z.to_numpy(np.float32, (B, cap))
+    n = d_n.to_numpy(np.int32, (B,))
+    total = {}
+    oL, oR = oracle.Extractor(nf), oracle.Extractor(nf)
+    for b in range(B):
+        rkL, _ = oL(scenes[b][0])
+        rkR, _ = oR(scenes[b][1])
+        assert rkL.tobytes() == raw["L"][1][b, :raw["L"][3][b]].tobytes(), b
+        assert rkR.tobytes() == raw["R"][1][b, :raw["R"][3][b]].tobytes(), b
+        kL, dL, kR, dR = sets[b]
+        ru, rz, rn, c = _oracle_and_model(oracle, oL, oR, kL, dL, kR, dR, mb, mbf, "pair %d" % b)
+        m = len(kL)
+        assert n[b] == rn, (b, n[b], rn)
+        assert u[b, :m].tobytes() == ru.tobytes() and z[b, :m].tobytes() == rz.tobytes(), b
+        assert (rn == 0) == (limits[b][0] == 0 or limits[b][1] == 0), (b, rn)
+        _add(total, c)
+    _tally_branches(tally, total)
+    exL.close()
+    exR.close()
+    for x in dev + [d_u, d_z, d_n, raw["L"][0], raw["R"][0]]:
+        x.free()
+
+
+@pytest.mark.gpu
+def test_hip_stereo_new_scenes_row_bin_overflow(oracle, tmp_path):
+    """The resampled, gain and planted scenes once more with ORBHIP_STEREO_ENT_PER_KP=1 (the scan over all right
+    keypoints of k_stereo_best); the variable is read once per process, hence the child."""
+    import os
+    import subprocess
+    import sys
+    import stereo_scenes as ss
+    here = os.path.dirname(os.path.abspath(__file__))
+    cases = [("gain", 90), ("slant25", 91), ("maxd", 92)]
+    code = (
+        "import sys, numpy as np\n"
+        "sys.path[:0] = [%r, %r, %r]\n"
+        "import stereo_scenes as ss, test_stereo as t\n"
+        "from orbhip.extractor import ComputeStereoMatches, ORBextractor\n"
+        "W, H, nf, mb, mbf = ss.EUROC\n"
+        "a, b = ORBextractor(nf, max_w=W, max_h=H), ORBextractor(nf, max_w=W, max_h=H)\n"
+        "out = {}\n"
+        "for i, (kind, seed) in enumerate(%r):\n"
+        "    L, R, plants, kmb, kmbf = ss.scene(kind, seed, W, H, mb, mbf)\n"
+        "    kL, dL = a(L); kR, dR = b(R)\n"
+        "    kL, dL, kR, dR = ss.plant_zero(kL, dL, kR, dR, plants, seed)\n"
+        "    out['u%%d' %% i], out['z%%d' %% i], out['n%%d' %% i] = ComputeStereoMatches(a, kL, dL, b, kR, dR, kmb, kmbf)\n"
+        "p = [c for c in t._planted_cases() if c[0] == 'cut273'][0][1]\n"
+        "a(p.left); b(p.right)\n"
+        "kL, dL, kR, dR = p.arrays()\n"
+        "out['uk'], out['zk'], out['nk'] = ComputeStereoMatches(a, kL, dL, b, kR, dR, p.mb, p.mbf)\n"
+        "np.savez(%r, **out)\n" % (here, os.path.join(os.path.dirname(here), "vi-orb-slam-icra2018_amd"),
+                                   os.path.join(os.path.dirname(here), "oracle"), cases, str(tmp_path / "o.npz")))
+    env = dict(os.environ, ORBHIP_STEREO_ENT_PER_KP="1")
+    subprocess.run([sys.executable, "-c", code], env=env, check=True, timeout=300)
+    got = np.load(tmp_path / "o.npz")
+    W, H, nf, mb, mbf = ss.EUROC
+    oL, oR = oracle.Extractor(nf), oracle.Extractor(nf)
+    for i, (kind, seed) in enumerate(cases):
+        L, R, plants, kmb, kmbf = ss.scene(kind, seed, W, H, mb, mbf)
+        kL, dL = oL(L)
+        kR, dR = oR(R)
+        kL, dL, kR, dR = ss.plant_zero(kL, dL, kR, dR, plants, seed)
+        ru, rz, rn = oracle.stereo_matches(oL, kL, dL, oR, kR, dR, kmb, kmbf)
+        assert int(got["n%d" % i]) == rn and rn > 100, kind
+        assert got["u%d" % i].tobytes() == ru.tobytes() and got["z%d" % i].tobytes() == rz.tobytes(), kind
+    name, p, n_want = [c for c in _planted_cases() if c[0] == "cut273"][0]
+    _check_want(name + " (HIP, overflow)", p, got["uk"], got["zk"], int(got["nk"]), n_want)

@@ -37,6 +37,7 @@
 // Bound: nominally HBM (reads and writes one byte per pixel; halo re-reads 64/58 x 160/128); measured: the lifetime of a
 // workgroup (load latency + matrix chain + store) at four workgroups per CU.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <cmath>
@@ -102,19 +103,6 @@ __device__ __forceinline__ BlurGeom blur_geom(const OrbLevels &G, const BlurTile
 // buffer: the second tile travels while the first is computed.  Order of one workgroup (no wait ever covers a store):
 //     request tile 0, tile 1, the tables | wait tile 0 | compute 0 | wait tile 1 | store 0 | compute 1 | store 1
 #define BM_TPW 2
-
-// one global_load_lds_dwordx4: 16 bytes per lane from its own address to LDS byte address ldsAddr + 16 * lane.  As inline
-// assembly: the builtin makes hipcc wait vmcnt(0) before every LDS access that might alias the destination (here: every
-// read of the OTHER buffer), which serialises the transfers and drains them before the compute phase; the waits are ours.
-// M0 carries the LDS address and is restored.
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t ldsAddr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(ldsAddr)
-                 : "memory");
-}
 
 // A transfer carries FOUR WHOLE ROWS of the chunk-linear image (4 x 13 chunks = 52 of the 64 lanes; 16 transfers per tile, four
 // per wave): a lane's (row of the four, chunk) is then the same for every transfer, the global address of transfer t is the

@@ -18,6 +18,7 @@
 //      outside the three dominant bins (:267-285), all in the workgroup.
 // Integer/bitwise path (XOR + popcount); no MFMA.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #include <type_traits>
 
@@ -27,23 +28,9 @@
 
 #define BS_THREADS 1024   // threads per workgroup of k_bow_seq (its launch bound)
 
-// 16 bytes per lane from global memory straight into LDS at (ldsAddr + 16 * lane); M0 carries the LDS address and is restored
-__device__ __forceinline__ void bs_glds16(const void *gsrc, uint32_t ldsAddr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(ldsAddr)
-                 : "memory");
-}
-
 struct BsBest {
     int b1, pos, b2;
 };
-
-__device__ __forceinline__ int bs_wave_min(int v) { return orb_wave_min_i(v); }
-// minimum over the 16 lanes of a DPP row, result in every lane of the row
-__device__ __forceinline__ int bs_row_min(int v) { return orb_row_min_i(v); }
 
 // first position in sorted keys[0..n) whose node (high 32 bits) is >= / > node
 __device__ __forceinline__ int bs_bound(const unsigned long long *keys, int n, unsigned node, bool upper)
@@ -184,7 +171,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
             const int nchunk = (side ? n2 : n1) * 2;
             const uint32_t ldsBase = (uint32_t)(uintptr_t)(side ? ls2 : ls1);
             for (int base = wv * 64; base < nchunk; base += nw * 64)
-                if (base + lane < nchunk) bs_glds16(src + (size_t)(base + lane) * 16, ldsBase + (uint32_t)base * 16u);
+                if (base + lane < nchunk) glds16(src + (size_t)(base + lane) * 16, ldsBase + (uint32_t)base * 16u);
         }
     }
     // only indices < max(n1, n2) hold keys: sort the smallest power of two that covers them
@@ -298,6 +285,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                     BsBest B = {256, 0x7FFFFFFF, 256};
 #pragma unroll
                     for (int c = 0; c < NC; c++) {
+                        // written out: hamming256() here changes the kernel's instructions
                         const int d = __popc(q0.x ^ r0[c].x) + __popc(q0.y ^ r0[c].y) + __popc(q0.z ^ r0[c].z) + __popc(q0.w ^ r0[c].w) +
                                       __popc(q1.x ^ r1[c].x) + __popc(q1.y ^ r1[c].y) + __popc(q1.z ^ r1[c].z) + __popc(q1.w ^ r1[c].w);
                         if (avail[c]) {
@@ -311,8 +299,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                         }
                     }
                     const int key = B.b1 < 256 ? ((B.b1 << 16) | B.pos) : 0x7FFFFFFF;
-                    const int k1 = bs_wave_min(key);
-                    const int k2 = bs_wave_min(key == k1 ? B.b2 : B.b1);
+                    const int k1 = wave_min(key);
+                    const int k2 = wave_min(key == k1 ? B.b2 : B.b1);
                     const int b1 = k1 == 0x7FFFFFFF ? 256 : (k1 >> 16), b2 = k2;
                     const bool pass = th_mode ? (b1 < th) : (b1 <= th);
                     if (pass && (float)b1 < nnratio * (float)b2) {
@@ -339,7 +327,6 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                 if (!((vbit1[i1 >> 5] >> (i1 & 31)) & 1u)) continue;   // no (good) MapPoint: :193-199
                 const uint4 q0 = LDSD ? ls1[2 * i1] : reinterpret_cast<const uint4 *>(d1)[2 * i1];
                 const uint4 q1 = LDSD ? ls1[2 * i1 + 1] : reinterpret_cast<const uint4 *>(d1)[2 * i1 + 1];
-                const uint32_t Q[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
                 BsBest B = {256, 0x7FFFFFFF, 256};
                 for (int p = s2 + lane; p < e2; p += 64) {
                     const int i2 = (int)(unsigned)key2[p];
@@ -347,8 +334,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                     if (th_mode && !((vbit2[i2 >> 5] >> (i2 & 31)) & 1u)) continue;   // KF-KF variant: :572-578
                     const uint4 r0 = LDSD ? ls2[2 * i2] : reinterpret_cast<const uint4 *>(d2)[2 * i2];
                     const uint4 r1 = LDSD ? ls2[2 * i2 + 1] : reinterpret_cast<const uint4 *>(d2)[2 * i2 + 1];
-                    const int d = __popc(Q[0] ^ r0.x) + __popc(Q[1] ^ r0.y) + __popc(Q[2] ^ r0.z) + __popc(Q[3] ^ r0.w) +
-                                  __popc(Q[4] ^ r1.x) + __popc(Q[5] ^ r1.y) + __popc(Q[6] ^ r1.z) + __popc(Q[7] ^ r1.w);
+                    const int d = hamming256(q0, q1, r0, r1);
                     if (d < B.b1) {
                         B.b2 = B.b1;
                         B.b1 = d;
@@ -360,8 +346,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                 // best = minimum of (distance, position) over the lanes; second = minimum of the best lane's own
                 // second and the other lanes' bests
                 const int key = B.b1 < 256 ? ((B.b1 << 16) | B.pos) : 0x7FFFFFFF;
-                const int k1 = bs_wave_min(key);
-                const int k2 = bs_wave_min(key == k1 ? B.b2 : B.b1);
+                const int k1 = wave_min(key);
+                const int k2 = wave_min(key == k1 ? B.b2 : B.b1);
                 const int b1 = k1 == 0x7FFFFFFF ? 256 : (k1 >> 16), b2 = k2;
                 const bool pass = th_mode ? (b1 < th) : (b1 <= th);
                 if (pass && (float)b1 < nnratio * (float)b2) {
@@ -412,6 +398,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                         if (th_mode && !((vbit2[i2 >> 5] >> (i2 & 31)) & 1u)) continue;   // KF-KF variant: :572-578
                         const uint4 r0 = LDSD ? ls2[2 * i2] : reinterpret_cast<const uint4 *>(d2)[2 * i2];
                         const uint4 r1 = LDSD ? ls2[2 * i2 + 1] : reinterpret_cast<const uint4 *>(d2)[2 * i2 + 1];
+                        // written out: hamming256() here changes the kernel's instructions
                         const int d = __popc(Q[0] ^ r0.x) + __popc(Q[1] ^ r0.y) + __popc(Q[2] ^ r0.z) + __popc(Q[3] ^ r0.w) +
                                       __popc(Q[4] ^ r1.x) + __popc(Q[5] ^ r1.y) + __popc(Q[6] ^ r1.z) + __popc(Q[7] ^ r1.w);
                         if (d < B.b1) {
@@ -423,8 +410,8 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
                         }
                     }
                     const int key = B.b1 < 256 ? ((B.b1 << 16) | B.pos) : 0x7FFFFFFF;
-                    const int k1 = bs_row_min(key);
-                    const int k2 = bs_row_min(key == k1 ? B.b2 : B.b1);
+                    const int k1 = row_min(key);
+                    const int k2 = row_min(key == k1 ? B.b2 : B.b1);
                     const int b1 = k1 == 0x7FFFFFFF ? 256 : (k1 >> 16), b2 = k2;
                     const bool pass = th_mode ? (b1 < th) : (b1 <= th);
                     if (pass && (float)b1 < nnratio * (float)b2) {
@@ -539,6 +526,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
 #define BL_TILES 640     // 16 x 16 tiles of the byte matrices per frame pair (~200 at 1000 features)
 #define BL_MAXN2 128   // side-2 features of a node the matrix paths take (8 candidates per lane of a 16-lane group)
 
+// hamming256() with the operands by reference: the by-value form changes k_bow_lane's instructions
 __device__ __forceinline__ int bl_dist(const uint4 &q0, const uint4 &q1, const uint4 &r0, const uint4 &r1)
 {
     return __popc(q0.x ^ r0.x) + __popc(q0.y ^ r0.y) + __popc(q0.z ^ r0.z) + __popc(q0.w ^ r0.w) + __popc(q1.x ^ r1.x) +
@@ -859,8 +847,8 @@ __global__ __launch_bounds__(BL_THREADS, 3) void k_bow_lane(const uint8_t *__res
                     k1 = min(k1, key);
                     k2 = nk2;
                 }
-                const int K1 = bs_row_min((int)k1);
-                const int K2 = bs_row_min((int)(k1 == (unsigned)K1 ? k2 : k1));
+                const int K1 = row_min((int)k1);
+                const int K2 = row_min((int)(k1 == (unsigned)K1 ? k2 : k1));
                 const int bd1 = K1 >> 8, bd2 = K2 >> 8, pos = K1 & 0xFF;
                 const bool pass = th_mode ? (bd1 < th) : (bd1 <= th);
                 if (pass && (float)bd1 < nnratio * (float)bd2) {        // ref: :228-230 / :598-600
@@ -990,8 +978,8 @@ __global__ __launch_bounds__(BL_THREADS, 3) void k_bow_lane(const uint8_t *__res
                 }
             }
             const int key = B.b1 < 256 ? ((B.b1 << 16) | B.pos) : 0x7FFFFFFF;
-            const int k1 = bs_wave_min(key);
-            const int k2 = bs_wave_min(key == k1 ? B.b2 : B.b1);
+            const int k1 = wave_min(key);
+            const int k2 = wave_min(key == k1 ? B.b2 : B.b1);
             const int bd1 = k1 == 0x7FFFFFFF ? 256 : (k1 >> 16), bd2 = k2;
             const bool pass = th_mode ? (bd1 < th) : (bd1 <= th);
             if (pass && (float)bd1 < nnratio * (float)bd2) {

@@ -15,6 +15,7 @@
 //    all angles k/64 degrees), so a = cos(angle), b = sin(angle) are bit-identical to the host.
 //  * x*b + y*a is two products and one sum, each rounded (no contraction) -- Appendix A7.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 #include "orb_pattern_data.h"
 #include "orb_trig.h"
 
@@ -50,18 +51,6 @@ __device__ __forceinline__ float fast_atan2_dev(float y, float x)
     if (x < 0) a = __fsub_rn(180.f, a);
     if (y < 0) a = __fsub_rn(360.f, a);
     return a;
-}
-
-// Sum over the 64 lanes, result wave-uniform.  DPP inside each row of 16 lanes (quad swaps, half
-// mirror, mirror), then the four row sums through v_readlane: no LDS round trips.
-__device__ __forceinline__ int wave_sum(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);   // row_half_mirror
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);   // row_mirror
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
 }
 
 // One 256-thread workgroup per DS_KP slots (16 for batches) of the per-frame level-keypoint array:
@@ -400,11 +389,7 @@ __global__ __launch_bounds__(256, 8) void k_describe(const OrbLevels G, const ui
 #pragma unroll
         for (int it = 0; it < DS_TRIPS; it++) {
             const uint8_t *src = p + (unsigned)(__mul24(prow[it], bstride) + 4 * pdw[it]);
-            uint32_t keep;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(src), "s"(__builtin_amdgcn_readfirstlane((int)(ldsAddr + 256u * (uint32_t)it)))
-                         : "memory");
+            glds4(src, __builtin_amdgcn_readfirstlane((int)(ldsAddr + 256u * (uint32_t)it)));
         }
         return true;
     };
@@ -581,15 +566,6 @@ constexpr DfBands make_df_bands()
 __constant__ __attribute__((aligned(16))) DfBands c_df_bands = make_df_bands();
 static_assert(df_half_bits(18 * 256) == 0x6C80 && df_half_bits(55 * 256) == 0x72E0 && df_half_bits(18) == 0x4C80 && df_half_bits(55) == 0x52E0, "binary16 of tap * 256, tap");
 
-__device__ __forceinline__ void df_glds16(const void *gsrc, uint32_t ldsAddr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(ldsAddr)
-                 : "memory");
-}
-
 __global__ __launch_bounds__(256, DF_WG_PER_CU) void k_describe_blur(const OrbLevels G, const uint8_t *__restrict__ lvl0, int stride0,
                                                           unsigned long long frame0, const uint8_t *__restrict__ pyr,
                                                           unsigned long long pyrFrame, const uint32_t *__restrict__ lvlKp,
@@ -676,7 +652,7 @@ __global__ __launch_bounds__(256, DF_WG_PER_CU) void k_describe_blur(const OrbLe
 #pragma unroll
             for (int t = 0; t < 3; t++)
                 if (lane < (t < 2 ? 63 : 18))
-                    df_glds16(src + (unsigned)__mul24(stageRow[t], stride), __builtin_amdgcn_readfirstlane((int)(ldsBase + 1008u * (uint32_t)t)));
+                    glds16(src + (unsigned)__mul24(stageRow[t], stride), __builtin_amdgcn_readfirstlane((int)(ldsBase + 1008u * (uint32_t)t)));
             return true;
         }
 #pragma unroll
@@ -685,7 +661,7 @@ __global__ __launch_bounds__(256, DF_WG_PER_CU) void k_describe_blur(const OrbLe
             y = y < 0 ? -y : y;                      // BORDER_REFLECT_101 of the level's rows (|excursion| <= 2)
             y = y >= h ? 2 * h - 2 - y : y;
             const uint8_t *src = img + (size_t)(unsigned)(__mul24(y, stride) + xc);
-            if (lane < (t < 2 ? 63 : 18)) df_glds16(src, __builtin_amdgcn_readfirstlane((int)(ldsBase + 1008u * (uint32_t)t)));
+            if (lane < (t < 2 ? 63 : 18)) glds16(src, __builtin_amdgcn_readfirstlane((int)(ldsBase + 1008u * (uint32_t)t)));
         }
         return true;
     };

@@ -19,6 +19,7 @@
 // (algorithmic bytes = sum_l (w_l-32)(h_l-32) per frame); measured bound is vector-instruction issue
 // (DESIGN.md section 4).
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -146,29 +147,6 @@ __device__ __forceinline__ int fast_score_dark(const uint8_t *pix, int off, int 
 __device__ __forceinline__ int fast_score_pol(const uint8_t *p, int pitch, int t)
 {
     return fast_score_win<false>(p, -3 * pitch - 3, pitch, t, nullptr);
-}
-
-// 16 bytes per lane from global memory straight into LDS at (ldsAddr + 16 * lane): global_load_lds_dwordx4 in assembly (the
-// builtin makes hipcc wait vmcnt(0) at every LDS access that might alias); M0 carries the LDS address and is restored.
-__device__ __forceinline__ void glds16(const void *gsrc, uint32_t ldsAddr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(ldsAddr)
-                 : "memory");
-}
-
-// inclusive wave prefix sum on the DPP network (row shifts, then the row totals of the lower rows)
-__device__ __forceinline__ int wave_incl_scan_dpp(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);   // row_shr:8
-    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = (int)(threadIdx.x & 63) >> 4;
-    return v + (row > 0 ? t0 : 0) + (row > 1 ? t1 : 0) + (row > 2 ? t2 : 0);
 }
 
 // Append the lanes with `flag` set to an LDS list (order irrelevant); returns the slot or -1.
@@ -596,7 +574,7 @@ __global__ __launch_bounds__(256, 8) void k_fast(const OrbLevels G, const uint8_
         // one wave per cell, one lane per row: the row prefix is a wave scan of the row popcounts
         for (int cj = tid >> 6; cj < T.ncells; cj += 4) {
             const int n = lane < DH ? __popcll(s_bits[cj * DH + lane]) : 0;
-            const int incl = wave_incl_scan_dpp(n);
+            const int incl = wave_incl_scan(n);
             if (lane < DH) s_pre[cj * DH + lane] = incl - n;
             if (lane == 63) s_cellCnt[cj] = incl;
         }
@@ -1270,7 +1248,7 @@ __global__ __launch_bounds__(256, 8) void k_fast_fix(const uint8_t *__restrict__
         // row -- no survivor is ever compared with another one.
         unsigned long long bits = lane < DH ? s_bits[cj * DH + lane] : 0ull;
         const int n = __popcll(bits);
-        const int incl = wave_incl_scan_dpp(n);
+        const int incl = wave_incl_scan(n);
         int rank = incl - n;
         if (lane == 63) cntRun[cj] = (uint16_t)incl;
         uint32_t *slotp = candRun + __mul24(cj, T.cellCap);

@@ -17,6 +17,7 @@
 //                   closed (that row is redone); then the rotation histogram.  A point with more candidates than
 //                   the list holds is rescanned exactly as the reference does it.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #define GCOLS ORBHIP_GRID_COLS
 #define GROWS ORBHIP_GRID_ROWS
@@ -39,18 +40,6 @@ __device__ __forceinline__ int grid_cell(const GridParams &gp, float x, float y)
     const int px = (int)roundf(__fmul_rn(__fsub_rn(x, gp.minX), gp.invW));   // :728-729
     const int py = (int)roundf(__fmul_rn(__fsub_rn(y, gp.minY), gp.invH));
     return (px < 0 || px >= GCOLS || py < 0 || py >= GROWS) ? -1 : px * GROWS + py;
-}
-
-// inclusive prefix sum over the 64 lanes on the DPP network
-__device__ __forceinline__ int grid_wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);
-    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = (int)(threadIdx.x & 63) >> 4;
-    return v + (row > 0 ? t0 : 0) + (row > 1 ? t1 : 0) + (row > 2 ? t2 : 0);
 }
 
 // LDSIDX: the cell entries are sorted in LDS (cap * 4 bytes of dynamic LDS) and written out once -- the insertion sort on the
@@ -106,7 +95,7 @@ __global__ __launch_bounds__(NT) void k_grid_build(const orbhip_keypoint *__rest
         c[k] = s_cnt[tid * PER + k];
         sum += c[k];
     }
-    const int incl = grid_wave_incl_scan(sum);
+    const int incl = wave_incl_scan(sum);
     if ((tid & 63) == 63) s_wtot[tid >> 6] = incl;
     __syncthreads();
     int run = incl - sum;
@@ -215,12 +204,6 @@ __global__ __launch_bounds__(256) void k_area_list(const orbhip_keypoint *__rest
     outCnt[iq] = n;
 }
 
-__device__ __forceinline__ int hamming256g(const uint4 a0, const uint4 a1, const uint4 r0, const uint4 r1)
-{
-    return __popc(a0.x ^ r0.x) + __popc(a0.y ^ r0.y) + __popc(a0.z ^ r0.z) + __popc(a0.w ^ r0.w) + __popc(a1.x ^ r1.x) +
-           __popc(a1.y ^ r1.y) + __popc(a1.z ^ r1.z) + __popc(a1.w ^ r1.w);
-}
-
 // The features of a frame in CSR order as compact records {x, y, octave | index << 8}: the window walk of
 // k_proj_cands then reads consecutive 16-byte records instead of following cell entry -> keypoint (two dependent
 // memory round trips per examined feature).
@@ -281,7 +264,7 @@ __global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__res
                     if (ur > 0 && fabsf(__fsub_rn(q.proj_xr, ur)) > q.radius) return;   // :92-97, :1418-1424
                 }
                 if (count < keff) {
-                    const int d = hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]);
+                    const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                     T[count] = (uint32_t)d | (((uint32_t)oct & 15u) << 9) | ((uint32_t)idx << 13);
                 }
                 count++;
@@ -322,11 +305,7 @@ __global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restric
             for (int cb = x0; cb <= x1; cb += 16) {
                 const int ix = cb + gl;
                 const int s = ix <= x1 ? O[ix * GROWS + y0] : 0, e = ix <= x1 ? O[ix * GROWS + y1 + 1] : 0;
-                int incl = e - s;
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);   // row_shr:1
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);
+                const int incl = row_incl_scan(e - s);
                 s_start[row][gl] = s;
                 s_excl[row][gl + 1] = incl;
                 if (gl == 0) s_excl[row][0] = 0;
@@ -350,7 +329,7 @@ __global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restric
                             if (ur > 0 && fabsf(__fsub_rn(q.proj_xr, ur)) > q.radius) pass = false;   // :92-97, :1418-1424
                         }
                         if (pass) {
-                            const int d = hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]);
+                            const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                             tup = (uint32_t)d | (((uint32_t)oct & 15u) << 9) | ((uint32_t)idx << 13);
                         }
                     }
@@ -415,7 +394,7 @@ __global__ __launch_bounds__(256) void k_window_best(const uint8_t *__restrict__
                         }
                         if ((double)__fmul_rn(e2, gate.invSigma2[oct & 15]) > lim) continue;
                     }
-                    const int d = hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]);
+                    const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                     if (d < bd) {
                         bd = d;
                         bi = idx;
@@ -426,16 +405,6 @@ __global__ __launch_bounds__(256) void k_window_best(const uint8_t *__restrict__
     }
     bestIdx[(size_t)b * capQ + iq] = bi;
     bestDist[(size_t)b * capQ + iq] = bd;
-}
-
-// minimum over the 16 lanes of a DPP row, result in every lane of the row
-__device__ __forceinline__ int row_min_i(int v)
-{
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xF, 0xF, false));
-    v = min(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xF, 0xF, false));
-    return v;
 }
 
 // k_window_best for ONE key frame per call: a 16-lane row per point (see k_proj_cands_row); the first feature of smallest
@@ -466,11 +435,7 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
             for (int cb = x0; cb <= x1; cb += 16) {
                 const int ix = cb + gl;
                 const int s = ix <= x1 ? O[ix * GROWS + y0] : 0, e = ix <= x1 ? O[ix * GROWS + y1 + 1] : 0;
-                int incl = e - s;
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xF, 0xF, true);
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xF, 0xF, true);
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xF, 0xF, true);
-                incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xF, 0xF, true);
+                const int incl = row_incl_scan(e - s);
                 s_start[row][gl] = s;
                 s_excl[row][gl + 1] = incl;
                 if (gl == 0) s_excl[row][0] = 0;
@@ -497,7 +462,7 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
                         }
                         if ((double)__fmul_rn(e2, gate.invSigma2[oct & 15]) > lim) continue;
                     }
-                    const int d = hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]);
+                    const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                     const int k = (d << 20) | (seen + r);
                     if (d < 256 && k < key) {
                         key = k;
@@ -509,7 +474,7 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
             }
         }
     }
-    const int k1 = row_min_i(key);
+    const int k1 = row_min_inactive_ok(key);
     if (key == k1 && k1 != 0x7FFFFFFF) {   // one lane: positions are unique
         bestIdx[(size_t)b * capQ + iq] = myIdx;
         bestDist[(size_t)b * capQ + iq] = k1 >> 20;
@@ -518,19 +483,6 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
         bestIdx[(size_t)b * capQ + iq] = -1;
         bestDist[(size_t)b * capQ + iq] = 256;
     }
-}
-
-__device__ __forceinline__ int wave_min_i(int v) { return orb_wave_min_i(v); }
-
-
-__device__ __forceinline__ int wave_sum_g(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
 }
 
 
@@ -622,9 +574,9 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
                     const int idx = (int)(t >> 13);
                     const bool ok = rowLive && gl < mycq && !((s_occ[idx >> 5] >> (idx & 31)) & 1u);
                     const int key = ok ? (int)(((t & 511u) << 6) | (uint32_t)gl) : 0x7FFFFFFF;
-                    const int k1 = row_min_i(key);
+                    const int k1 = row_min_inactive_ok(key);
                     const int l1 = k1 & 15;
-                    const int k2 = row_min_i((gl == l1 || k1 == 0x7FFFFFFF) ? 0x7FFFFFFF : key);
+                    const int k2 = row_min_inactive_ok((gl == l1 || k1 == 0x7FFFFFFF) ? 0x7FFFFFFF : key);
                     const uint32_t t1 = (uint32_t)__shfl((int)t, (g << 4) + l1);
                     const uint32_t t2 = (uint32_t)__shfl((int)t, (g << 4) + (k2 & 15));
                     const int bDist = k1 == 0x7FFFFFFF ? 256 : (k1 >> 6), bLevel = (int)((t1 >> 9) & 15u), bIdx = (int)(t1 >> 13);
@@ -676,10 +628,10 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
                 const int idx = (int)(t >> 13);
                 const bool ok = lane < c && !((s_occ[idx >> 5] >> (idx & 31)) & 1u);
                 const int key = ok ? (int)(((t & 511u) << 6) | (uint32_t)lane) : 0x7FFFFFFF;
-                const int k1 = wave_min_i(key);
+                const int k1 = wave_min(key);
                 if (k1 != 0x7FFFFFFF) {
                     const int l1 = k1 & 63;
-                    const int k2 = wave_min_i(lane == l1 ? 0x7FFFFFFF : key);
+                    const int k2 = wave_min(lane == l1 ? 0x7FFFFFFF : key);
                     const uint32_t t1 = (uint32_t)__builtin_amdgcn_readlane((int)t, l1);
                     bestDist = k1 >> 6;
                     bestLevel = (int)((t1 >> 9) & 15u);
@@ -701,7 +653,7 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
                         const float ur = UR[idx];
                         if (ur > 0 && fabsf(__fsub_rn(q.proj_xr, ur)) > q.radius) return;
                     }
-                    const int d = hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]);
+                    const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                     if (d < bestDist) {
                         bestDist2 = bestDist;
                         bestDist = d;
@@ -780,7 +732,7 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
                 removed++;
             }
         }
-        nm -= wave_sum_g(removed);
+        nm -= wave_sum(removed);
         WAVE_LDS_SYNC();
     }
     for (int i = lane; i < cap; i += 64) match[(size_t)b * cap + i] = s_match[i];
@@ -858,8 +810,8 @@ __global__ __launch_bounds__(1024) void k_proj_assign_par(const orbhip_keypoint 
             const int key0 = ok0 ? (int)(((t0 & 511u) << 6) | (uint32_t)gl) : 0x7FFFFFFF;
             const int key1 = ok1 ? (int)(((t1 & 511u) << 6) | (uint32_t)(gl + 16)) : 0x7FFFFFFF;
             const int mine = min(key0, key1), other = max(key0, key1);
-            const int k1 = row_min_i(mine);
-            const int k2 = row_min_i(mine == k1 ? other : mine);       // keys are unique (position bits) unless both are "none"
+            const int k1 = row_min_inactive_ok(mine);
+            const int k2 = row_min_inactive_ok(mine == k1 ? other : mine);       // keys are unique (position bits) unless both are "none"
             const int p1 = k1 & 31, p2 = k2 & 31;
             const uint32_t w1 = (uint32_t)__shfl((int)(p1 >= 16 ? t1 : t0), (tid & 48) + (p1 & 15));
             const uint32_t w2 = (uint32_t)__shfl((int)(p2 >= 16 ? t1 : t0), (tid & 48) + (p2 & 15));
@@ -1039,7 +991,7 @@ __global__ __launch_bounds__(256) void k_init_cands(const orbhip_keypoint *__res
                     const int idx = w >> 8;
                     // tuple = distance << 23 | position in visiting order << 16 | feature of frame 2 (< 2^16): as an integer it
                     // orders by distance, then by position -- the reference's strict '<' scan takes the first of equal distances
-                    s_lst[wv][pos] = ((uint32_t)hamming256g(a0, a1, D[2 * idx], D[2 * idx + 1]) << 23) | ((uint32_t)pos << 16) | (uint32_t)idx;
+                    s_lst[wv][pos] = ((uint32_t)hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]) << 23) | ((uint32_t)pos << 16) | (uint32_t)idx;
                 }
                 count += __popcll(m);
             }
@@ -1110,7 +1062,7 @@ __global__ __launch_bounds__(INIT_NT) void k_init_assign(const orbhip_keypoint *
     auto round_rows = [&](int base) -> int {
         const int q = base + lane;
         const int c = q < n1 ? (staged ? s_tc[q] : TC[q]) : 0;
-        return -wave_min_i(-min(c, keff));
+        return -wave_min(-min(c, keff));
     };
     // a round's 64 lists, transposed (entry p of list l at [p * 64 + l]): rows [0, rows) are contiguous (a window of 100 pixels
     // holds ~30 level-0 features: ~10 of the 32 KB).  Thread t of nt; eight loads in flight and no branch around any of them
@@ -1180,7 +1132,7 @@ __global__ __launch_bounds__(INIT_NT) void k_init_assign(const orbhip_keypoint *
     // first -- three quarters of the rounds would be a barrier and nothing else
     int lastq = -1;
     for (int i = lane; i < n1; i += 64) lastq = (staged ? s_tc[i] : TC[i]) > 0 ? i : lastq;
-    lastq = -wave_min_i(-lastq);
+    lastq = -wave_min(-lastq);
     const int nWalk = min(n1, lastq + 1);
     int rows = rows0;
     for (int base = 0, r = 0; base < nWalk; base += 64, r++) {
@@ -1245,9 +1197,9 @@ __global__ __launch_bounds__(INIT_NT) void k_init_assign(const orbhip_keypoint *
                                 m2 = key;
                             }
                         }
-                        const int k1 = wave_min_i(m1);
+                        const int k1 = wave_min(m1);
                         if (k1 != 0x7FFFFFFF) {
-                            const int k2 = wave_min_i(m1 == k1 ? m2 : m1);   // list positions are unique: one lane holds k1
+                            const int k2 = wave_min(m1 == k1 ? m2 : m1);   // list positions are unique: one lane holds k1
                             bestDist = k1 >> 7;
                             bestIdx = (int)(tupb[(k1 & 127) * 64 + j] & 0xFFFFu);
                             if (k2 != 0x7FFFFFFF) bestDist2 = k2 >> 7;
@@ -1263,7 +1215,7 @@ __global__ __launch_bounds__(INIT_NT) void k_init_assign(const orbhip_keypoint *
                         const uint4 *qd = reinterpret_cast<const uint4 *>(desc1 + ((size_t)b * cap1 + i1) * 32);
                         const uint4 a0 = qd[0], a1 = qd[1];
                         walk_window(gp, q, K2, O, I, [&](int idx, int) {
-                            const int d = hamming256g(a0, a1, D2[2 * idx], D2[2 * idx + 1]);
+                            const int d = hamming256(a0, a1, D2[2 * idx], D2[2 * idx + 1]);
                             if (s_md[idx] <= d) return;
                             if (d < bestDist) {
                                 bestDist2 = bestDist;

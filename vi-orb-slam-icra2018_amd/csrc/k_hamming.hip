@@ -16,6 +16,7 @@
 //                serially (the reference's greedy claiming is order dependent), the 64 lanes scan
 //                the node's side-2 features in parallel and reduce with a tie-aware merge.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -23,14 +24,6 @@
 struct Best {
     int b1, idx, b2;
 };
-
-__device__ __forceinline__ int hamming256(const uint32_t q[8], const uint32_t r[8])
-{
-    int d = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) d += __popc(q[k] ^ r[k]);
-    return d;
-}
 
 // sequential update of ref: :216-226
 __device__ __forceinline__ void best_update(Best &B, int d, int j)
@@ -799,8 +792,8 @@ __global__ __launch_bounds__(256) void k_bow_match(const uint8_t *__restrict__ d
                     // of three shuffled values and six tie-aware merges was two thirds of a side-1 feature's instructions, and this
                     // loop is the serial chain the call waits for)
                     const int key = bpos != 0x7FFFFFFF ? ((bd1 << 8) | bpos) : 0x7FFFFFFF;
-                    const int k1 = orb_wave_min_i(key);
-                    const int k2 = orb_wave_min_i(key == k1 ? bd2 : bd1);
+                    const int k1 = wave_min(key);
+                    const int k2 = wave_min(key == k1 ? bd2 : bd1);
                     bd1 = k1 != 0x7FFFFFFF ? k1 >> 8 : 256;
                     bpos = k1 != 0x7FFFFFFF ? (k1 & 255) : 0x7FFFFFFF;
                     bd2 = k2;
@@ -860,8 +853,8 @@ __global__ __launch_bounds__(256) void k_bow_match(const uint8_t *__restrict__ d
         }
         {
             const int key = bpos != 0x7FFFFFFF ? ((bd1 << 20) | bpos) : 0x7FFFFFFF;   // (a FeatureVector of < 2^20 entries: orbhip_search_by_bow / _sets check)
-            const int k1 = orb_wave_min_i(key);
-            const int k2 = orb_wave_min_i(key == k1 ? bd2 : bd1);
+            const int k1 = wave_min(key);
+            const int k2 = wave_min(key == k1 ? bd2 : bd1);
             bd1 = k1 != 0x7FFFFFFF ? k1 >> 20 : 256;
             bpos = k1 != 0x7FFFFFFF ? (k1 & 0xFFFFF) : 0x7FFFFFFF;
             bd2 = k2;
@@ -996,7 +989,7 @@ __global__ __launch_bounds__(256) void k_tri_match(const orbhip_keypoint *__rest
                     if (!((double)dsqr < lim2[c])) continue;
                     key = min(key, (d << 16) | (0xFFFF - (c * 64 + lane)));
                 }
-                key = orb_wave_min_i(key);
+                key = wave_min(key);
                 if (key != 0x7FFFFFFF) {
                     const int pos = 0xFFFF - (key & 0xFFFF);
 #pragma unroll
@@ -1046,7 +1039,7 @@ __global__ __launch_bounds__(256) void k_tri_match(const orbhip_keypoint *__rest
             if (!((double)dsqr < __dmul_rn(3.84, (double)sigma2[k2.octave]))) continue;
             key = min(key, (d << 16) | (0xFFFF - min(p, 0xFFFF)));
         }
-        key = orb_wave_min_i(key);
+        key = wave_min(key);
         if (lane == 0 && key != 0x7FFFFFFF) match12[i1] = idx2[b0 + (0xFFFF - (key & 0xFFFF))];
     }
 }
@@ -1101,8 +1094,7 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
                 int cnt = 0;
                 for (int j = 0; j < N; j++) {
                     const uint4 b0 = D[2 * j], b1 = D[2 * j + 1];
-                    const int d = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-                                  __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+                    const int d = hamming256(a0, a1, b0, b1);
                     cnt += d <= mid;
                 }
                 if (cnt > k) hi = mid;

@@ -13,6 +13,7 @@
 // Measured and dropped: building two levels per launch (level l+1 kept in LDS, written once): -3 % before the
 // window hint, slower than one level per launch after it.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 
@@ -21,17 +22,6 @@ typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 // RZ_TH = rows of a tile (RZ_TH / 8 per thread): 32 for batches, 8 for a single frame or two (4x the workgroups)
 #define RZ_MAXCH 16    // 16-byte chunks per staged source row (source span <= 240 px + alignment)
 #define RZ_MAXROWS 44  // staged source rows
-
-// 16 bytes per lane from global memory straight into LDS at (ldsAddr + 16 * lane); M0 carries the LDS address and is restored
-// (assembly: the builtin makes hipcc wait vmcnt(0) at every LDS access that might alias).
-__device__ __forceinline__ void rz_glds16(const void *gsrc, uint32_t ldsAddr)
-{
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(ldsAddr)
-                 : "memory");
-}
 
 template <int RZ_TH>
 __global__ __launch_bounds__(256) void k_resize(const uint8_t *__restrict__ src, int sstride,
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t *__restrict__ src,
         const uint8_t *sp = S + (size_t)(symin + rl) * sstride + XA + (ch << 4);
         const uint32_t ldsBase = (uint32_t)(uintptr_t)&s_src[0][0];
         for (int rb = wv * 4; rb < nrows; rb += 16)
-            if (ch < nch && rb + rl < nrows) rz_glds16(sp + (size_t)rb * sstride, ldsBase + (uint32_t)(rb * (RZ_MAXCH * 16)));
+            if (ch < nch && rb + rl < nrows) glds16(sp + (size_t)rb * sstride, ldsBase + (uint32_t)(rb * (RZ_MAXCH * 16)));
     }
     // this thread's taps are requested before the barrier so that their latency overlaps the staging
     constexpr int NR = RZ_TH / 8;                 // output rows per thread (rows dy, dy + 8, ...)
@@ -102,11 +92,11 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t *__restrict__ src,
     if (TABDMA && grouped) {
         const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
         if (wv == 1) {
-            if (lane < 32) rz_glds16(ytab + min(oy0 + lane, dh - 1), (uint32_t)(uintptr_t)&s_ytab[0]);
+            if (lane < 32) glds16(ytab + min(oy0 + lane, dh - 1), (uint32_t)(uintptr_t)&s_ytab[0]);
         } else if (wv >= 2) {
             const int q = 64 * (wv - 2) + lane;                 // 16-byte chunk of the 32 x 3 group entries
             const int grp = q / 3, part = q - 3 * grp;
-            if (q < 96) rz_glds16(gtab + 3 * (min(ox0 + 4 * grp, dw - 1) >> 2) + part, (uint32_t)(uintptr_t)&s_gtab[64 * (wv - 2)]);
+            if (q < 96) glds16(gtab + 3 * (min(ox0 + 4 * grp, dw - 1) >> 2) + part, (uint32_t)(uintptr_t)&s_gtab[64 * (wv - 2)]);
         }
     } else {
 #pragma unroll
@@ -251,13 +241,13 @@ __global__ __launch_bounds__(256) void k_resize_fit(const uint8_t *__restrict__ 
         const uint8_t *sp = S + (size_t)(symin + rl) * sstride + XA + (ch << 4);
         const uint32_t ldsBase = (uint32_t)(uintptr_t)&s_src[0][0];
         for (int rb = wv * 4; rb < nrows; rb += 16)
-            if (ch < nch && rb + rl < nrows) rz_glds16(sp + (size_t)rb * sstride, ldsBase + (uint32_t)(rb * (RZ_MAXCH * 16)));
+            if (ch < nch && rb + rl < nrows) glds16(sp + (size_t)rb * sstride, ldsBase + (uint32_t)(rb * (RZ_MAXCH * 16)));
         if (wv == 1) {
-            if (lane < TH) rz_glds16(ytab + min(oy0 + lane, dh - 1), (uint32_t)(uintptr_t)&s_ytab[0]);
+            if (lane < TH) glds16(ytab + min(oy0 + lane, dh - 1), (uint32_t)(uintptr_t)&s_ytab[0]);
         } else if (wv >= 2) {
             const int q = 64 * (wv - 2) + lane;                 // 16-byte chunk of the twg x 3 group entries
             const int grp = q / 3, part = q - 3 * grp;
-            if (q < 3 * twg) rz_glds16(gtab + 3 * (min(ox0 + 4 * grp, dw - 1) >> 2) + part, (uint32_t)(uintptr_t)&s_gtab[64 * (wv - 2)]);
+            if (q < 3 * twg) glds16(gtab + 3 * (min(ox0 + 4 * grp, dw - 1) >> 2) + part, (uint32_t)(uintptr_t)&s_gtab[64 * (wv - 2)]);
         }
     }
     const int r = (int)(((unsigned)tid * (unsigned)rmagic) >> 16), g = tid - r * twg;   // tid / twg, tid % twg

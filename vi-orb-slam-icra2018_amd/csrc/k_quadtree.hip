@@ -4,6 +4,7 @@
 // workgroup execution model (LDS atomics, wave-shuffle scans) and the gather of the per-cell
 // candidate slots written by k_fast into the compact, canonically ordered point array.
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 #include "quadtree_core.h"
 
 #include <cstdlib>
@@ -18,18 +19,6 @@
 #define QT_GL 16   // ... lanes per cell (measured: 8 / 16 / 32 / 64 lanes x 4 / 8 / 16 pairs -- 16 x 4; 16 pairs cost registers, 64 lanes idle ones)
 #endif
 #define QT_LDS_LIMIT ((size_t)156 * 1024)   // node tables beyond this go to global memory (k_quadtree<.., true>)
-
-// inclusive prefix sum over the 64 lanes on the DPP network (row shifts, then the totals of the lower rows)
-__device__ __forceinline__ int qt_wave_incl_scan(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xF, 0xF, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xF, 0xF, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xF, 0xF, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xF, 0xF, true);   // row_shr:8
-    const int t0 = __builtin_amdgcn_readlane(v, 15), t1 = __builtin_amdgcn_readlane(v, 31), t2 = __builtin_amdgcn_readlane(v, 47);
-    const int row = (int)(threadIdx.x & 63) >> 4;
-    return v + (row > 0 ? t0 : 0) + (row > 1 ? t1 : 0) + (row > 2 ? t2 : 0);
-}
 
 // LAT: the single-frame variant (a handful of workgroups on the whole chip: every step is latency); the batch variant runs
 // thousands of workgroups beside the blur and wants the fewest instructions instead
@@ -46,7 +35,7 @@ struct QtBlock {
     // *p += sum of v over the workgroup; called by every thread (the wave sums go to the counter, one atomic per wave)
     __device__ __forceinline__ void reduce_add(int *p, int v) const
     {
-        const int incl = qt_wave_incl_scan(v);
+        const int incl = wave_incl_scan(v);
         if ((threadIdx.x & 63) == 63 && incl != 0) atomicAdd(p, incl);
     }
     // sum of v over each aligned group of 2^sl adjacent threads (sl <= 6: a group lies inside one wave); called by every thread
@@ -74,7 +63,7 @@ struct QtBlock {
                     v[k] = beg + k < end ? a[beg + k] : 0;
                     sum += v[k];
                 }
-                const int incl = qt_wave_incl_scan(sum);
+                const int incl = wave_incl_scan(sum);
                 int run = incl - sum;
 #pragma unroll
                 for (int k = 0; k < 8; k++) {
@@ -91,7 +80,7 @@ struct QtBlock {
         const int beg = min(t * K, n), end = min(beg + K, n);
         int sum = 0;
         for (int i = beg; i < end; i++) sum += a[i];
-        const int incl = qt_wave_incl_scan(sum);
+        const int incl = wave_incl_scan(sum);
         if (lane == 63) wtot[wave] = incl;
         __syncthreads();
         int base = 0, total = 0;

@@ -12,6 +12,7 @@
 //   k_stereo_cut     per stereo pair: median of the patch distances of the accepted matches by a two-level
 //                    histogram select, matches with distance >= 1.5f*1.4f*median are removed (:970-983).
 #include "orbhip_internal.h"
+#include "wave_ops.h"
 
 struct StereoGeom {
     int nlevels, nRows, stride0L, stride0R;
@@ -98,12 +99,6 @@ __global__ __launch_bounds__(256) void k_stereo_rows(const StereoGeom G, const o
     }
 }
 
-__device__ __forceinline__ int hamming256(const uint4 a0, const uint4 a1, const uint4 r0, const uint4 r1)
-{
-    return __popc(a0.x ^ r0.x) + __popc(a0.y ^ r0.y) + __popc(a0.z ^ r0.z) + __popc(a0.w ^ r0.w) + __popc(a1.x ^ r1.x) +
-           __popc(a1.y ^ r1.y) + __popc(a1.z ^ r1.z) + __popc(a1.w ^ r1.w);
-}
-
 __global__ __launch_bounds__(256) void k_stereo_best(const StereoGeom G, const orbhip_keypoint *__restrict__ kpsL,
                                                      const uint8_t *__restrict__ descL, const int32_t *__restrict__ cntL,
                                                      const orbhip_keypoint *__restrict__ kpsR,
@@ -164,16 +159,6 @@ __global__ __launch_bounds__(256) void k_stereo_best(const StereoGeom G, const o
     const bool found = bestKey < (100u << 16);
     bestUR[(size_t)b * cap + iL] = found ? kR[bestKey & 0xFFFF].x : -1.0f;      // uR0 of :897 (kpR.pt.x >= 0 always)
     bestDist[(size_t)b * cap + iL] = found ? (int)(bestKey >> 16) : 100;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x141, 0xF, 0xF, true);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x140, 0xF, 0xF, true);
-    return __builtin_amdgcn_readlane(v, 0) + __builtin_amdgcn_readlane(v, 16) + __builtin_amdgcn_readlane(v, 32) +
-           __builtin_amdgcn_readlane(v, 48);
 }
 
 __device__ __forceinline__ const uint8_t *stereo_level(const uint8_t *lvl0, int stride0, unsigned long long frame0,
@@ -261,7 +246,7 @@ __global__ __launch_bounds__(256) void k_stereo_refine(const StereoGeom G, const
                     const int cRb = s_R[5 * 24 + s + 6];
                     acc += (abs(a0 - ((int)r0[s + 1] - cRb)) + (has1 ? abs(a1 - ((int)r1[s + 1] - cRb)) : 0)) << 16;
                 }
-                const int tot = wave_sum_i(acc);
+                const int tot = wave_sum(acc);
                 dists[s] = tot & 0xFFFF;
                 if (s + 1 < 11) dists[s + 1] = (unsigned)tot >> 16;
             }

@@ -227,6 +227,7 @@ __global__ __launch_bounds__(256) void k_vocab_transform(const uint8_t *__restri
             }
 #pragma unroll
             for (int j = 0; j < VT_CHUNK; j++) {
+                // written out: hamming256() here changes the kernel's instructions
                 const unsigned d = __popc(a.x ^ p[j].x) + __popc(a.y ^ p[j].y) + __popc(a.z ^ p[j].z) + __popc(a.w ^ p[j].w) +
                                    __popc(b.x ^ q[j].x) + __popc(b.y ^ q[j].y) + __popc(b.z ^ q[j].z) + __popc(b.w ^ q[j].w);
                 const unsigned key = (d << 20) | (unsigned)(cb + j - c0);

@@ -3,7 +3,7 @@
 
 A step = one pass of the hot path over one batch of B synthetic frames resident in HBM -- B DISTINCT frames, the
 consecutive frames of one synthetic stream (round 6; rounds 1-5 tiled 32 frames to the batch, which is now the supplementary
-`tiled_check`), every one of them verified against the oracle outside the timed region:
+`tiled_check`), every one of them verified against the oracle outside the timed region by a --full run:
   * ORBextractor on all B frames (8-level pyramid, FAST-9/16 per cell, quadtree, IC angle, 7x7 blur,
     rBRIEF), then
   * the reference's frame-to-frame matching (Tracking::TrackReferenceKeyFrame): vocabulary transform of
@@ -17,9 +17,11 @@ the latency-bound stages of one part overlap the VALU-bound stages of another.
 N > 1: one process per GPU (torch.distributed, backend nccl = RCCL); frames are sharded, there is no
 per-frame collective; the ORB vocabulary blob is broadcast once at start-up over xGMI (not timed).
 
-Prints ONE JSON line on rank 0, last on stdout (driver contract), with `roofline` (FAST kernel) and,
-at N=1, `cpu_baseline` (the CPU oracle doing the same operations on this box's host cores, bounded
-sample).
+Prints ONE JSON line on rank 0, last on stdout (driver contract), with `roofline` (FAST kernel, from the HIP events of the
+timed steps themselves).  A plain run does only what that line's headline needs: set-up, warm-up, the timed steps, --dump-outputs
+and the line.  --full adds everything else, outside the timed region: the timed batch against the oracle, the per-stage times and
+rooflines (a pass of its own), at N=1 `cpu_baseline` (the CPU oracle doing the same operations on this box's host cores, bounded
+sample), the pipelined, host-fed and tiled figures, BASELINE.json's configs 2-5, the content classes and the batch sweep.
 """
 import argparse
 import ctypes as C
@@ -378,7 +380,7 @@ def batch_sweep(args):
     res = {}
     for mult in (2, 3):
         b = args.batch * mult
-        cmd = [sys.executable, os.path.abspath(__file__), "--batch", str(b), "--steps", "8", "--warmup", "2", "--match", args.match,
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--batch", str(b), "--steps", "8", "--warmup", "2", "--match", args.match,
                "--cpu-frames", "0", "--pipelined", "0", "--host-batch", "0", "--configs", "0", "--content", "0", "--tiled-check", "0",
                "--verify", "-1", "--batch-sweep", "0"]
         try:
@@ -900,6 +902,11 @@ def secondary_configs(device, blob):
     return out
 
 
+# the options of the supplementary figures and checks (the argument group `sup` of main): --full only
+SUPPLEMENTARY = ("pipelined", "cpu_frames", "host_batch", "configs", "content", "verify", "tiled_check", "no_tiling", "batch_sweep",
+                 "streams_config")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -910,44 +917,54 @@ def main():
                     "frame of the timed batch is a different frame of one synthetic stream); a smaller number is tiled to the batch")
     ap.add_argument("--match", choices=["bow", "brute", "both"], default="bow")
     ap.add_argument("--contexts", type=int, default=1, help="extractor contexts the batch is split over in the timed region")
-    ap.add_argument("--pipelined", type=int, default=2, help="also report the free-running throughput with this many "
-                    "contexts (0 = skip); supplementary, never `value`")
-    ap.add_argument("--cpu-frames", type=int, default=800, help="frames of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also make every supplementary figure and check "
+                    "below (off: set-up, warm-up, the timed steps, --dump-outputs and the result line, nothing else)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--oracle-worker", nargs=4, default=None, help=argparse.SUPPRESS)
-    ap.add_argument("--host-batch", type=int, default=256, help="frames per batch of the host-fed pipeline figure (0 = skip)")
-    ap.add_argument("--configs", type=int, default=1, help="also time BASELINE.json's configs 2-5 (outside the headline's timed "
-                    "region, each verified against the oracle); 0 = skip")
-    ap.add_argument("--content", type=int, default=1, help="also run the step on the synthetic content classes of orbhip/synth.py "
-                    "(textured, indoor_sparse, white_noise, low_contrast), each verified against the oracle; 0 = skip")
-    ap.add_argument("--verify", type=int, default=-1, help="frames of the timed batch whose GPU outputs are compared with "
-                    "the oracle outside the timed region (0 = skip; -1 = every distinct frame, by oracle processes on the host's "
-                    "cores, and the pair across the first tile boundary when the batch is tiled); a difference ends the run with exit "
-                    "code 3.  With one context every tiled copy is then compared ON THE DEVICE with its original, so that the whole "
-                    "timed batch is verified")
-    ap.add_argument("--tiled-check", type=int, default=1, help="also time a few steps on the first 32 frames TILED to the batch "
-                    "(the headline of rounds 1-5): what tiling gains; 0 = skip")
-    ap.add_argument("--no-tiling", type=int, default=None, help=argparse.SUPPRESS)   # rounds 1-5's name of the opposite check (tools/*.sh)
     ap.add_argument("--backend", choices=["nccl", "gloo"], default=os.environ.get("ORBHIP_BENCH_BACKEND", "nccl"),
                     help="torch.distributed backend of an N > 1 run; gloo only for ranks that share one device (tests): RCCL "
                     "refuses duplicate devices, the vocabulary then travels through host memory")
-    ap.add_argument("--batch-sweep", type=int, default=1, help="also time the same step at 2 and 3 times the batch in child processes "
-                    "(the headline stays at --batch: the profiles and every per-launch figure refer to it)")
-    ap.add_argument("--streams-config", type=int, default=-1, help="N > 1: also run BASELINE config 4 proper, one EuRoC stream per "
-                    "rank (-1 = when N >= 4; 1 = always; 0 = never)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (a fixed, seeded "
                     "sample of the batch's frames) to DIR/<name>.npy; see dump_outputs")
+    sup = ap.add_argument_group("supplementary figures and checks (--full only; each flag tunes or skips one of them)")
+    sup.add_argument("--pipelined", type=int, default=2, help="also report the free-running throughput with this many "
+                     "contexts (0 = skip); supplementary, never `value`")
+    sup.add_argument("--cpu-frames", type=int, default=800, help="frames of the CPU baseline sample (0 = skip)")
+    sup.add_argument("--host-batch", type=int, default=256, help="frames per batch of the host-fed pipeline figure (0 = skip)")
+    sup.add_argument("--configs", type=int, default=1, help="also time BASELINE.json's configs 2-5 (outside the headline's timed "
+                     "region, each verified against the oracle); 0 = skip")
+    sup.add_argument("--content", type=int, default=1, help="also run the step on the synthetic content classes of orbhip/synth.py "
+                     "(textured, indoor_sparse, white_noise, low_contrast), each verified against the oracle; 0 = skip")
+    sup.add_argument("--verify", type=int, default=-1, help="frames of the timed batch whose GPU outputs are compared with "
+                     "the oracle outside the timed region (0 = skip; -1 = every distinct frame, by oracle processes on the host's "
+                     "cores, and the pair across the first tile boundary when the batch is tiled); a difference ends the run with exit "
+                     "code 3.  With one context every tiled copy is then compared ON THE DEVICE with its original, so that the whole "
+                     "timed batch is verified")
+    sup.add_argument("--tiled-check", type=int, default=1, help="also time a few steps on the first 32 frames TILED to the batch "
+                     "(the headline of rounds 1-5): what tiling gains; 0 = skip")
+    sup.add_argument("--no-tiling", type=int, default=None, help=argparse.SUPPRESS)   # rounds 1-5's name of the opposite check
+    sup.add_argument("--batch-sweep", type=int, default=1, help="also time the same step at 2 and 3 times the batch in child processes "
+                     "(the headline stays at --batch: the profiles and every per-launch figure refer to it)")
+    sup.add_argument("--streams-config", type=int, default=-1, help="N > 1: also run BASELINE config 4 proper, one EuRoC stream per "
+                     "rank (-1 = when N >= 4; 1 = always; 0 = never)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.no_tiling is not None:
-        args.tiled_check = args.no_tiling
     if args.cpu_worker:
         cpu_worker(args.cpu_worker, args.cpu_frames, args.match)
         return
     if args.oracle_worker:
         oracle_worker(args.oracle_worker[0], int(args.oracle_worker[1]), int(args.oracle_worker[2]), args.match, args.oracle_worker[3])
         return
+    if not args.full:
+        # a plain run makes none of the supplementary figures: a flag of theirs without --full is a mistake, not a no-op
+        given = ["--" + name.replace("_", "-") for name in SUPPLEMENTARY if getattr(args, name) != ap.get_default(name)]
+        if given:
+            ap.error("%s: supplementary figures and checks run with --full only" % ", ".join(given))
+        for name in SUPPLEMENTARY:
+            setattr(args, name, 0)                                  # 0 skips each of them
+    if args.no_tiling is not None:
+        args.tiled_check = args.no_tiling
 
     # ---- one process per GPU ----
     # Under a launcher (torch.distributed.run sets RANK / WORLD_SIZE) this process is one rank.  Without one,
@@ -1118,19 +1135,20 @@ def main():
     dt = time.perf_counter() - t0
     # what the last timed step computed, copied out before anything below runs the step again
     last_step = snapshot_outputs(ctxs, use_bow, args.match) if (args.dump_outputs and rank == 0) else None
-    for ex, _ in ctxs:
-        assert L.orbhip_set_stage_timing(ex.handle, 2) == 0
-    stage_pass = max(1, min(5, args.steps))
+    stage_pass = max(1, min(5, args.steps)) if args.full else 0     # --full: every stage's time, in steps of their own
     fast_instrumented = 0.0
-    for _ in range(stage_pass):
-        step()
+    if stage_pass:
         for ex, _ in ctxs:
-            ms = (C.c_float * 6)()
-            assert L.orbhip_get_stage_times(ex.handle, ms) == 0
-            for i in (0, 2, 3, 4, 5):
-                stage[i] += ms[i] * max(args.steps, 1) / stage_pass
-            fast_instrumented += ms[1] / stage_pass
-    barrier()
+            assert L.orbhip_set_stage_timing(ex.handle, 2) == 0
+        for _ in range(stage_pass):
+            step()
+            for ex, _ in ctxs:
+                ms = (C.c_float * 6)()
+                assert L.orbhip_get_stage_times(ex.handle, ms) == 0
+                for i in (0, 2, 3, 4, 5):
+                    stage[i] += ms[i] * max(args.steps, 1) / stage_pass
+                fast_instrumented += ms[1] / stage_pass
+        barrier()
     per_rank_dt = [float(x) for x in gather_objects(dist, dt, world)]
     dt = max(per_rank_dt)                                      # the MAX over ranks is the job's time
     stage /= max(args.steps, 1)
@@ -1240,6 +1258,9 @@ def main():
             "bow_matches_per_frame": None if nmatch is None else round(nmatch, 1),
             "brute_matches_le_TH_LOW_per_frame": None if nbrute is None else round(nbrute, 1),
         }
+        if not stage_pass:                  # every figure but k_fast's comes from the stage pass
+            for key in ("rooflines", "stage_ms", "stage_ms_note"):
+                del out[key]
         if world == 1 and args.pipelined > 1 and B % args.pipelined == 0:
             out["pipelined"] = pipelined_throughput(args, d_img, blob if use_bow else None, local_rank, cap)
         if world == 1 and args.host_batch > 0:
@@ -1264,7 +1285,7 @@ def main():
     v_copies = verify_tiled_copies(ctxs[0][1], U, Bc, cap, args.match) if (NC == 1 and U < Bc and v_oracle >= min(U + 1, Bc)) else 0
     t_ver = time.perf_counter() - t_ver
     v_all = gather_objects(dist, (v_oracle, v_copies), world)
-    if out is not None:
+    if out is not None and args.full:
         out["verified_frames"] = v_oracle + v_copies
         out["verified_vs_oracle"] = v_oracle
         out["verified_copies_vs_original"] = v_copies

@@ -1,10 +1,12 @@
-"""bench.py keeps the driver's contract: ONE JSON line, last on stdout, with the required keys, `roofline` and
-`cpu_baseline` (small batch / few steps so that it runs in seconds)."""
+"""bench.py keeps the driver's contract: ONE JSON line, last on stdout, with the required keys and `roofline`; a plain run makes
+that line and nothing else, --full adds `cpu_baseline` and every other supplementary figure and check (small batch / few steps so
+that it runs in seconds)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_roofline_and_cpu_baseline():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "64",
                           "--cpu-frames", "40", "--pipelined", "0"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -65,6 +67,35 @@ def _bench(args, env=None, timeout=600):
                           timeout=timeout, env=e)
 
 
+SUPPLEMENTARY_KEYS = ("cpu_baseline", "cpu_baseline_all_cores", "speedup_vs_cpu_1core", "verified_frames", "verified_vs_oracle",
+                      "pipelined", "host_fed", "tiled_check", "configs", "roofline_mfma", "content", "batch_sweep", "rooflines",
+                      "stage_ms")
+
+
+@pytest.mark.gpu
+def test_a_plain_bench_run_makes_the_headline_and_nothing_else(tmp_path):
+    """Without --full: set-up, warm-up, the timed steps, --dump-outputs and the line -- the same headline fields, no supplementary
+    figure or check."""
+    out = _bench(["--steps", "2", "--warmup", "1", "--batch", "64", "--dump-outputs", str(tmp_path / "dump")])
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+    assert d["metric"] == "ORB extract+match frames/sec @640x480/1000 feat" and d["unit"] == "frames/s" and d["dtype"] == "u8"
+    assert d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert d["value"] > 1000 and abs(d["value"] - 64 / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    assert d["roofline"]["kernel"] == "k_fast" and d["roofline"]["achieved"] > 0 and d["keypoints_per_frame"] > 500
+    assert not [k for k in SUPPLEMENTARY_KEYS if k in d], d.keys()
+    assert "verified_frames" not in d["config"] and "host_fed_frames_per_s" not in d["config"]
+    counts = np.load(tmp_path / "dump" / "counts.npy")
+    assert counts.shape == (64,) and (counts > 500).all()
+
+
+def test_a_supplementary_flag_without_full_is_refused():
+    """A plain run makes no supplementary figure, so asking for one (or for its absence) without --full is an error, reported
+    before anything touches a GPU."""
+    out = _bench(["--steps", "2", "--verify", "8", "--cpu-frames", "0"], timeout=120)
+    assert out.returncode == 2 and "--cpu-frames, --verify" in out.stderr and "--full" in out.stderr
+
+
 def test_gpus_n_starts_n_ranks_itself_cpu_gloo():
     """`bench.py --gpus 2` without a launcher starts two fresh rank processes (RANK / WORLD_SIZE / MASTER_* set,
     127.0.0.1 rendezvous) before touching any GPU; checked here on CPU with the launcher self-test (gloo)."""
@@ -96,7 +127,7 @@ def test_launch_ranks_reports_a_failing_rank():
 def test_bench_distributed_code_path_on_one_gpu():
     """ORBHIP_BENCH_FORCE_DIST=1: process group (nccl = RCCL, world 1), vocabulary broadcast into a device buffer and
     the vocabulary load from that buffer -- the N > 1 code path of bench.py on the one GPU the box has."""
-    out = _bench(["--steps", "2", "--warmup", "1", "--batch", "64", "--cpu-frames", "0", "--pipelined", "0", "--configs", "0",
+    out = _bench(["--full", "--steps", "2", "--warmup", "1", "--batch", "64", "--cpu-frames", "0", "--pipelined", "0", "--configs", "0",
                   "--content", "0", "--streams-config", "1"], env={"ORBHIP_BENCH_FORCE_DIST": "1"})
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
@@ -127,7 +158,7 @@ def test_bench_two_ranks_sharing_device_0():
     the vocabulary travels through host memory): sharded frames, max-over-ranks time, every rank's whole batch verified, the
     host-fed mode on both ranks at once, config 4's streams split over the ranks."""
     from orbhip import distributed as D
-    rc, out = D.launch_ranks([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2",
+    rc, out = D.launch_ranks([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--backend", "gloo", "--steps", "2",
                               "--warmup", "1", "--batch", "64", "--pipelined", "0", "--streams-config", "1"], 2, timeout=900,
                              local_ranks=[0, 0])
     assert rc == 0, out[-3000:]
@@ -140,7 +171,7 @@ def test_bench_two_ranks_sharing_device_0():
 
 @pytest.mark.gpu
 def test_bench_brute_match_is_verified_too():
-    out = _bench(["--steps", "1", "--warmup", "1", "--batch", "16", "--cpu-frames", "0", "--pipelined", "0", "--match", "both",
+    out = _bench(["--full", "--steps", "1", "--warmup", "1", "--batch", "16", "--cpu-frames", "0", "--pipelined", "0", "--match", "both",
                   "--verify", "6"])
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $REPO
-python bench.py > $OUT/bench_stdout.txt 2> $OUT/bench_stderr.txt
+python bench.py --full > $OUT/bench_stdout.txt 2> $OUT/bench_stderr.txt
 tail -1 $OUT/bench_stdout.txt > $OUT/bench.json
 # counters first (summarize_prof.py merges fast_valu.json into traffic.json)
 bash tools/pmc_gpu.sh util "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_BUSY_CYCLES" 2>&1 | grep -E "^k_" > $OUT/counters_sq.txt

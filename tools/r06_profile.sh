@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd $REPO
-python bench.py > $OUT/bench_stdout.txt 2> $OUT/bench_stderr.txt
+python bench.py --full > $OUT/bench_stdout.txt 2> $OUT/bench_stderr.txt
 tail -1 $OUT/bench_stdout.txt > $OUT/bench.json
 bash tools/pmc_gpu.sh util "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_BUSY_CYCLES" 2>&1 | grep -E "^k_" > $OUT/counters_sq.txt
 bash tools/pmc_gpu.sh util2 "GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_I8 SQ_VALU_MFMA_BUSY_CYCLES" 2>&1 | grep -E "^k_" > $OUT/counters_misc.txt
@@ -45,15 +45,15 @@ bash tools/bow_ablate.sh > $OUT/bow_ablate_time.txt 2>&1                   # k_b
 # k_describe_blur by phase (stops: 0 slot decode; 1 + disc loads and moments; 2 + angles; 3 + staging and blur; 4 everything; 5 = everything
 # but the disc loads) in the default schedule; then by occupancy
 for p in 0 1 2 3 4 5; do
-  ORBHIP_DESCRIBE_PHASES=$p python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stop<=$p describe_ms', d['stage_ms']['describe'], 'quadtree_ms', d['stage_ms']['quadtree'], 'frames/s', d['value'])"
+  ORBHIP_DESCRIBE_PHASES=$p python bench.py --full --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('stop<=$p describe_ms', d['stage_ms']['describe'], 'quadtree_ms', d['stage_ms']['quadtree'], 'frames/s', d['value'])"
 done > $OUT/describe_blur_ablate.txt 2>&1
 for pad in 0 8192 16384 28000; do
-  ORBHIP_DESCRIBE_PADLDS=$pad python bench.py --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('unused LDS $pad describe_ms', d['stage_ms']['describe'])"
+  ORBHIP_DESCRIBE_PADLDS=$pad python bench.py --full --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('unused LDS $pad describe_ms', d['stage_ms']['describe'])"
 done >> $OUT/describe_blur_ablate.txt 2>&1
 # the two-kernel path of rounds 1-5 (k_blur + k_describe) in the same call, for the comparison
-ORBHIP_DESCRIBE_FUSED=0 python bench.py --cpu-frames 0 --pipelined 0 --verify -1 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('k_blur + k_describe (ORBHIP_DESCRIBE_FUSED=0):', d['value'], 'frames/s', d['stage_ms'], 'verified', d['verified_frames'])" >> $OUT/describe_blur_ablate.txt 2>&1
+ORBHIP_DESCRIBE_FUSED=0 python bench.py --full --cpu-frames 0 --pipelined 0 --verify -1 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 --tiled-check 0 --steps 10 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('k_blur + k_describe (ORBHIP_DESCRIBE_FUSED=0):', d['value'], 'frames/s', d['stage_ms'], 'verified', d['verified_frames'])" >> $OUT/describe_blur_ablate.txt 2>&1
 for p in 1 2 3 4 5 8; do
-  echo -n "stop<=$p "; ORBHIP_FAST_PHASES=$p bash tools/pmc_gpu.sh ab$p "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT" --steps 2 --warmup 1 --batch 1024 --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 2>&1 | grep -E "^k_fast"
+  echo -n "stop<=$p "; ORBHIP_FAST_PHASES=$p bash tools/pmc_gpu.sh ab$p "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT" --steps 2 --warmup 1 --batch 1024 --full --cpu-frames 0 --pipelined 0 --verify 0 --host-batch 0 --configs 0 --content 0 --batch-sweep 0 2>&1 | grep -E "^k_fast"
 done > $OUT/fast_ablate_pmc.txt 2>&1
 timeout 300 bash tools/pmc_gpu.sh l2 "TCC_HIT_sum TCC_MISS_sum TCP_TCC_READ_REQ_sum TCP_TCC_WRITE_REQ_sum" 2>&1 | grep -E "^k_" > $OUT/counters_l2.txt
 python tools/percall_latency.py > $OUT/percall_table.md 2> $OUT/percall_stderr.txt

@@ -158,7 +158,7 @@ extern "C" int orbhip_knn2_allgather_merge_device(orbhip_ctx *c, const void *d_b
     const size_t part = (size_t)3 * nq + 1;
     int rc;
     if ((rc = orb_match_scratch(c, (part * (size_t)(c->nranks + 1)) * 4 + 256))) return rc;
-    int32_t *mine = (int32_t *)c->d_match, *all = mine + part;
+    int32_t *mine = c->d_match.as<int32_t>(), *all = mine + part;
     hipStream_t s = c->stream;
     HIPCHK(c, hipMemcpyAsync(mine, d_best_idx_local, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(c, hipMemcpyAsync(mine + nq, d_best_d_local, (size_t)nq * 4, hipMemcpyDeviceToDevice, s));

@@ -1,5 +1,5 @@
 // api_common.h -- shared by the api_*.hip files that implement the C ABI of liborbhip.so (include/orbhip.h): error
-// reporting, grow-only buffers and the two staging helpers of the host-pointer entry points.
+// reporting, the context's grow-only buffers and the two staging helpers of the host-pointer entry points.
 #ifndef ORBHIP_API_COMMON_H
 #define ORBHIP_API_COMMON_H
 #include "orbhip_internal.h"
@@ -9,6 +9,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <mutex>
 
 // records the message (in the context, or process-wide when there is none) and returns `code` (api_extract.hip)
@@ -34,18 +35,13 @@ static inline hipError_t orb_enter(const orbhip_ctx *c)
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-template <class T>
-static int ensure(orbhip_ctx *c, T *&ptr, size_t &cap, size_t need)
+// a pipeline buffer of the context (orb_configure) of at least `need` bytes
+static int ensure(orbhip_ctx *c, OrbBlock &b, size_t need)
 {
-    if (need <= cap && ptr) return ORBHIP_OK;
-    if (ptr) HIPCHK(c, hipFree(ptr));
-    ptr = nullptr;
-    cap = 0;
-    c->allocGen++;   // a captured single-frame graph holds the old pointer: its replay key includes the generation
-    void *p = nullptr;
-    HIPCHK(c, hipMalloc(&p, need ? need : 16));
-    ptr = reinterpret_cast<T *>(p);
-    cap = need;
+    bool moved = false;
+    const hipError_t e = b.grow(need, need, &moved);
+    if (moved) c->allocGen++;   // a captured single-frame graph holds the old pointer: its replay key includes the generation
+    if (e != hipSuccess) return fail(c, ORBHIP_E_HIP, std::string("device buffer allocation: ") + hipGetErrorString(e));
     return ORBHIP_OK;
 }
 
@@ -53,9 +49,11 @@ static int ensure(orbhip_ctx *c, T *&ptr, size_t &cap, size_t need)
 int orb_configure(orbhip_ctx *c, int w, int h, int stride0, int B);
 int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t frame0, int B, orbhip_keypoint *d_kps,
                      uint8_t *d_desc, int32_t *d_counts, int cap, uint8_t *h_pyr_dst = nullptr);
-void orb_graph_release(orbhip_ctx *c);
+int orb_graph_run(orbhip_ctx *c, OrbGraph &g, const void *key, size_t keyBytes, const std::function<int()> &enqueue,
+                  const char *failMsg);
 int orb_host_stage(orbhip_ctx *c, size_t bytes);                  // page-locked result block c->h_stage of at least `bytes`
 int orb_host_pyr_stage(orbhip_ctx *c, int B, uint8_t **dst);      // page-locked pyramid copy (or nullptr when not asked for)
+int orb_host_in_stage(orbhip_ctx *c, size_t bytes, OrbGraph *also = nullptr);   // page-locked input c->h_in of at least `bytes`
 // api_frame.hip
 void orb_frame_release(orbhip_ctx *c);
 // api_pipe.hip / api_comm.hip: what orbhip_destroy releases
@@ -79,7 +77,7 @@ struct TmpDev {
     orbhip_ctx *c;
     uint8_t *base = nullptr;
     size_t used = 0, cap = 0;
-    std::vector<void *> extra;   // blocks taken beyond the reserved size (a reserve() total that undercounts must not
+    std::vector<OrbBlock> extra; // blocks taken beyond the reserved size (a reserve() total that undercounts must not
                                  // become a null pointer handed to a copy: ADVICE r01)
     bool bad = false;            // an overflow block could not be allocated: take() returned null, the entry point must
                                  // return ORBHIP_E_HIP before it copies anything (TMPCHK) -- the drop-in never terminates
@@ -90,24 +88,14 @@ struct TmpDev {
         // Every entry point synchronises before its normal return; an early error return may leave asynchronous copies from
         // the caller's (or this frame's stack) memory in flight -- drain them before that memory goes away.
         if (c && c->stream && hipStreamQuery(c->stream) != hipSuccess) (void)hipStreamSynchronize(c->stream);
-        for (void *p : extra) (void)hipFree(p);
     }
     int reserve(size_t bytes)
     {
         bytes += 4096;
-        if (bytes > c->d_tmp_bytes || !c->d_tmp) {
-            if (c->d_tmp) {
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                HIPCHK(c, hipFree(c->d_tmp));
-            }
-            c->d_tmp = nullptr;
-            c->d_tmp_bytes = 0;
-            const size_t want = bytes + bytes / 2;
-            HIPCHK(c, hipMalloc(&c->d_tmp, want));
-            c->d_tmp_bytes = want;
-        }
-        base = (uint8_t *)c->d_tmp;
-        cap = c->d_tmp_bytes;
+        if (c->d_tmp && bytes > c->d_tmp.bytes()) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the last call may still read it)
+        HIPCHK(c, c->d_tmp.grow(bytes, bytes + bytes / 2));
+        base = c->d_tmp.as<uint8_t>();
+        cap = c->d_tmp.bytes();
         return ORBHIP_OK;
     }
     void *take(size_t bytes)
@@ -119,14 +107,14 @@ struct TmpDev {
             return p;
         }
         // beyond the reservation: a block of its own (slow, but never a null or overlapping pointer)
-        void *p = nullptr;
-        if (hipMalloc(&p, bytes ? bytes : 16) != hipSuccess) {
+        OrbBlock b;
+        if (b.grow(bytes) != hipSuccess) {
             (void)hipGetLastError();
             bad = true;
             return nullptr;
         }
-        extra.push_back(p);
-        return p;
+        extra.push_back(std::move(b));
+        return extra.back().as<void>();
     }
 };
 
@@ -150,18 +138,10 @@ struct Packed {
         total += 8192;
         int rc;
         if ((rc = T.reserve(total))) return rc;
-        if (total > c->h_pack_bytes) {
-            if (c->h_pack) HIPCHK(c, hipHostFree(c->h_pack));
-            c->h_pack = nullptr;
-            c->h_pack_bytes = 0;
-            void *p = nullptr;
-            HIPCHK(c, hipHostMalloc(&p, total + total / 2, hipHostMallocDefault));
-            c->h_pack = (uint8_t *)p;
-            c->h_pack_bytes = total + total / 2;
-        }
+        HIPCHK(c, c->h_pack.grow(total, total + total / 2));
         d = (uint8_t *)T.take(total);
         TMPCHK(c, T);
-        h = c->h_pack;
+        h = c->h_pack.as<uint8_t>();
         cap = total;
         return ORBHIP_OK;
     }

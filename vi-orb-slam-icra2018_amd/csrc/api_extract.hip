@@ -79,17 +79,18 @@ int orb_configure(orbhip_ctx *c, int w, int h, int stride0, int B)
             c->chainGroups.clear();
         }
         int rc2;
-        if ((rc2 = ensure(c, c->d_resizeTab, c->cap_resize, all.size() * 4 + 16))) return rc2;
-        if ((rc2 = ensure(c, c->d_fastTiles, c->cap_fastTiles, c->fastTiles.size() * sizeof(FastTile)))) return rc2;
-        if ((rc2 = ensure(c, c->d_blurTiles, c->cap_blurTiles, c->blurTiles.size() * sizeof(BlurTile)))) return rc2;
-        if ((rc2 = ensure(c, c->d_chainTiles, c->cap_chainTiles, c->chainTiles.size() * sizeof(ChainTile) + 16))) return rc2;
+        if ((rc2 = ensure(c, c->d_resizeTab, all.size() * 4 + 16))) return rc2;
+        if ((rc2 = ensure(c, c->d_fastTiles, c->fastTiles.size() * sizeof(FastTile)))) return rc2;
+        if ((rc2 = ensure(c, c->d_blurTiles, c->blurTiles.size() * sizeof(BlurTile)))) return rc2;
+        if ((rc2 = ensure(c, c->d_chainTiles, c->chainTiles.size() * sizeof(ChainTile) + 16))) return rc2;
         if (!c->chainTiles.empty())
-            HIPCHK(c, hipMemcpyAsync(c->d_chainTiles, c->chainTiles.data(), c->chainTiles.size() * sizeof(ChainTile),
+            HIPCHK(c, hipMemcpyAsync(c->d_chainTiles.as<ChainTile>(), c->chainTiles.data(),
+                                     c->chainTiles.size() * sizeof(ChainTile),
                                      hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_resizeTab, all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_fastTiles, c->fastTiles.data(), c->fastTiles.size() * sizeof(FastTile),
+        HIPCHK(c, hipMemcpyAsync(c->d_resizeTab.as<int32_t>(), all.data(), all.size() * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_fastTiles.as<FastTile>(), c->fastTiles.data(), c->fastTiles.size() * sizeof(FastTile),
                                  hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_blurTiles, c->blurTiles.data(), c->blurTiles.size() * sizeof(BlurTile),
+        HIPCHK(c, hipMemcpyAsync(c->d_blurTiles.as<BlurTile>(), c->blurTiles.data(), c->blurTiles.size() * sizeof(BlurTile),
                                  hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // the host vectors above go out of scope
     }
@@ -97,31 +98,24 @@ int orb_configure(orbhip_ctx *c, int w, int h, int stride0, int B)
     const OrbLevels &G = c->G;
     const size_t Bm = (size_t)c->max_batch;  // buffers are sized for the context's batch once
     int rc;
-    if ((rc = ensure(c, c->d_pyr, c->cap_pyr, Bm * c->pyrFrameBytes))) return rc;
-    if ((rc = ensure(c, c->d_blur, c->cap_blur, Bm * (c->lvl0FrameBytes + c->pyrFrameBytes)))) return rc;
-    if ((rc = ensure(c, c->d_cand, c->cap_cand, Bm * (size_t)G.totalCands * 4))) return rc;
-    if ((rc = ensure(c, c->d_cellCnt, c->cap_cells, Bm * (size_t)G.totalCells * 2 + 64))) return rc;
-    if ((rc = ensure(c, c->d_pts, c->cap_pts, Bm * (size_t)G.totalPts * 4))) return rc;
-    if ((rc = ensure(c, c->d_pnode, c->cap_pnode, Bm * (size_t)G.totalPts * 4))) return rc;
-    if ((rc = ensure(c, c->d_lvlKp, c->cap_kps, Bm * (size_t)G.totalKps * 4))) return rc;
-    if ((rc = ensure(c, c->d_lvlAngle, c->cap_angle, Bm * (size_t)G.totalKps * 4))) return rc;
-    if ((rc = ensure(c, c->d_lvlCandCnt, c->cap_cnt1, Bm * ORBHIP_MAX_LEVELS * 4))) return rc;
-    if ((rc = ensure(c, c->d_lvlKpCnt, c->cap_cnt2, Bm * ORBHIP_MAX_LEVELS * 4))) return rc;
-    if ((rc = ensure(c, c->d_lvl0, c->cap_lvl0, Bm * c->lvl0FrameBytes))) return rc;
+    if ((rc = ensure(c, c->d_pyr, Bm * c->pyrFrameBytes))) return rc;
+    if ((rc = ensure(c, c->d_blur, Bm * (c->lvl0FrameBytes + c->pyrFrameBytes)))) return rc;
+    if ((rc = ensure(c, c->d_cand, Bm * (size_t)G.totalCands * 4))) return rc;
+    if ((rc = ensure(c, c->d_cellCnt, Bm * (size_t)G.totalCells * 2 + 64))) return rc;
+    if ((rc = ensure(c, c->d_pts, Bm * (size_t)G.totalPts * 4))) return rc;
+    if ((rc = ensure(c, c->d_pnode, Bm * (size_t)G.totalPts * 4))) return rc;
+    if ((rc = ensure(c, c->d_lvlKp, Bm * (size_t)G.totalKps * 4))) return rc;
+    if ((rc = ensure(c, c->d_lvlAngle, Bm * (size_t)G.totalKps * 4))) return rc;
+    if ((rc = ensure(c, c->d_lvlCandCnt, Bm * ORBHIP_MAX_LEVELS * 4))) return rc;
+    if ((rc = ensure(c, c->d_lvlKpCnt, Bm * ORBHIP_MAX_LEVELS * 4))) return rc;
+    if ((rc = ensure(c, c->d_lvl0, Bm * c->lvl0FrameBytes))) return rc;
     // quadtree node tables of levels whose feature quota exceeds what the LDS holds (about 2000 features on one level)
     if (const size_t qt = quadtree_table_scratch_bytes(G, (int)Bm))
-        if ((rc = ensure(c, c->d_qtTables, c->cap_qtTables, qt))) return rc;
+        if ((rc = ensure(c, c->d_qtTables, qt))) return rc;
     if ((size_t)G.outCap > c->cap_out) {
-        size_t d1 = 0, d2 = 0;
-        if (c->d_kps) HIPCHK(c, hipFree(c->d_kps));
-        if (c->d_desc) HIPCHK(c, hipFree(c->d_desc));
-        c->d_kps = nullptr;
-        c->d_desc = nullptr;
         // one block for keypoints | descriptors | counts of a call (carved per call for its B, orbhip_extract_batch):
         // the results of the host-pointer API come back in ONE device-to-host copy
-        if ((rc = ensure(c, c->d_kps, d1, Bm * (size_t)G.outCap * (sizeof(orbhip_keypoint) + 32) + Bm * 4 + 1024))) return rc;
-        c->allocGen++;
-        (void)d2;
+        if ((rc = ensure(c, c->d_kps, Bm * (size_t)G.outCap * (sizeof(orbhip_keypoint) + 32) + Bm * 4 + 1024))) return rc;
         c->cap_out = (size_t)G.outCap;
     }
     return ORBHIP_OK;
@@ -174,8 +168,9 @@ extern "C" orbhip_ctx *orbhip_create(int device, int nfeatures, float scaleFacto
     {
         uint32_t bands[6 * 64 * 4];
         blur_band_table(bands);
-        if ((e = hipMalloc((void **)&c->d_blurBands, sizeof(bands))) != hipSuccess) return bail("hipMalloc", e);
-        if ((e = hipMemcpy(c->d_blurBands, bands, sizeof(bands), hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy", e);
+        if ((e = c->d_blurBands.grow(sizeof(bands))) != hipSuccess) return bail("hipMalloc", e);
+        if ((e = hipMemcpy(c->d_blurBands.as<uint32_t>(), bands, sizeof(bands),
+                           hipMemcpyHostToDevice)) != hipSuccess) return bail("hipMemcpy", e);
     }
     // size everything for the largest image now, so per-frame calls never allocate
     const int stride0 = (int)align_up((size_t)max_w, 64);
@@ -197,18 +192,10 @@ extern "C" void orbhip_destroy(orbhip_ctx *c)
     orb_pipe_release(c);
     orb_sets_release(c);
     orb_kfdb_release(c);
-    orb_graph_release(c);
+    c->graph.release();
     orb_frame_release(c);
-    if (c->h_in) (void)hipHostFree(c->h_in);
-    if (c->h_pyr) (void)hipHostFree(c->h_pyr);
-    void *bufs[] = {c->d_lvl0, c->d_pyr, c->d_blur, c->d_cand, c->d_cellCnt, c->d_pts, c->d_pnode,
-                    c->d_lvlCandCnt, c->d_lvlKp, c->d_lvlKpCnt, c->d_lvlAngle, c->d_kps, c->d_desc,
-                    c->d_counts, c->d_qtTables, c->d_fastTiles, c->d_blurTiles, c->d_blurBands, c->d_chainTiles, c->d_resizeTab, c->d_match, c->d_maps, c->d_tmp};
-    for (void *b : bufs)
-        if (b) (void)hipFree(b);
+    static_cast<OrbCtxBuffers &>(*c) = OrbCtxBuffers();   // every buffer, before the streams go
     c->vocHold.reset();   // (the block itself lives on while another context borrows it)
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    if (c->h_pack) (void)hipHostFree(c->h_pack);
     for (int i = 0; i < 8; i++)
         if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     for (int i = 0; i < 3; i++)
@@ -295,24 +282,29 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     const bool chained = B < 8 && !noChain && !c->chainGroups.empty();
     if (chained)
         for (const ChainGroup &grp : c->chainGroups)
-            launch_pyramid_chain(s, G, c->chainLevels, grp, c->d_chainTiles, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes,
-                                 c->d_resizeTab, B, h_pyr_dst);   // (the host copy of the pyramid is written by the kernel itself)
+            launch_pyramid_chain(s, G, c->chainLevels, grp, c->d_chainTiles.as<ChainTile>(), lvl0, stride0, frame0,
+                                 c->d_pyr.as<uint8_t>(), c->pyrFrameBytes,
+                                 c->d_resizeTab.as<int32_t>(), B,
+                                 h_pyr_dst);   // (the host copy of the pyramid is written by the kernel itself)
     // batches: level l from level l-1 (sequential dependency), all frames per launch
     static const bool fitTiles = ORB_TUNE("RESIZE_FIT", 1) != 0;   // batches: tiles fitted to the level (k_resize_fit)
     for (int l = 1; l < G.nlevels && !chained; l++) {
         const OrbLevel &S = G.lv[l - 1], &D = G.lv[l];
-        const uint8_t *src = (l == 1) ? lvl0 : c->d_pyr + S.imgOff;
+        const uint8_t *src = (l == 1) ? lvl0 : c->d_pyr.as<uint8_t>() + S.imgOff;
         const int sstride = (l == 1) ? stride0 : S.stride;
         const size_t sframe = (l == 1) ? frame0 : c->pyrFrameBytes;
         if (fitTiles && B >= 8 && c->resizeFit[l].ntx > 0) {
-            launch_resize_fit(s, src, S.w, S.h, sstride, sframe, c->d_pyr + D.imgOff, D.w, D.h, D.stride, c->pyrFrameBytes,
-                              c->d_resizeTab + c->resizeTabOff[l][1], c->d_resizeTab + c->resizeTabOff[l][2], c->resizeFit[l], B);
+            launch_resize_fit(s, src, S.w, S.h, sstride, sframe, c->d_pyr.as<uint8_t>() + D.imgOff, D.w, D.h, D.stride,
+                              c->pyrFrameBytes,
+                              c->d_resizeTab.as<int32_t>() + c->resizeTabOff[l][1],
+                              c->d_resizeTab.as<int32_t>() + c->resizeTabOff[l][2], c->resizeFit[l], B);
             continue;
         }
-        launch_resize(s, src, S.w, S.h, sstride, sframe, c->d_pyr + D.imgOff, D.w, D.h, D.stride,
-                      c->pyrFrameBytes, c->d_resizeTab + c->resizeTabOff[l][0],
-                      c->d_resizeTab + c->resizeTabOff[l][1],
-                      c->resizeGroups[l] ? c->d_resizeTab + c->resizeTabOff[l][2] : nullptr, c->resizeHint[l][B >= 8 ? 0 : 1], B);
+        launch_resize(s, src, S.w, S.h, sstride, sframe, c->d_pyr.as<uint8_t>() + D.imgOff, D.w, D.h, D.stride,
+                      c->pyrFrameBytes, c->d_resizeTab.as<int32_t>() + c->resizeTabOff[l][0],
+                      c->d_resizeTab.as<int32_t>() + c->resizeTabOff[l][1],
+                      c->resizeGroups[l] ? c->d_resizeTab.as<int32_t>() + c->resizeTabOff[l][2] : nullptr,
+                      c->resizeHint[l][B >= 8 ? 0 : 1], B);
     }
     if (evFast) HIPCHK(c, hipEventRecord(c->ev[1], s));
     // host copy of levels 1.. (orbhip_set_host_pyramid): one copy of the B frames' pyramid block into pinned memory.  A
@@ -323,7 +315,8 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     if (pyrFork) {
         HIPCHK(c, hipEventRecord(c->evp[0], s));
         HIPCHK(c, hipStreamWaitEvent(c->stream2, c->evp[0], 0));
-        HIPCHK(c, hipMemcpyAsync(h_pyr_dst, c->d_pyr, (size_t)B * c->pyrFrameBytes, hipMemcpyDeviceToHost, c->stream2));
+        HIPCHK(c, hipMemcpyAsync(h_pyr_dst, c->d_pyr.as<uint8_t>(), (size_t)B * c->pyrFrameBytes, hipMemcpyDeviceToHost,
+                                 c->stream2));
         HIPCHK(c, hipEventRecord(c->evp[1], c->stream2));
     }
     // E3 FAST, E4 quadtree, E6 blur, E5 + E7 describe.  FAST runs ALONE on the device (it is the kernel whose roofline is
@@ -342,36 +335,48 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     const size_t blurFrame = c->lvl0FrameBytes + c->pyrFrameBytes;
     const bool fusedDescribe = describe_blur_available(G, B);   // (never below 8 frames)
     auto blur_all = [&](hipStream_t st) {
-        launch_blur(st, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_blur, blurFrame, c->d_blurTiles,
-                    (int)c->blurTiles.size(), c->d_blurBands, B);
+        launch_blur(st, G, lvl0, stride0, frame0, c->d_pyr.as<uint8_t>(), c->pyrFrameBytes, c->d_blur.as<uint8_t>(), blurFrame,
+                    c->d_blurTiles.as<BlurTile>(),
+                    (int)c->blurTiles.size(), c->d_blurBands.as<uint32_t>(), B);
     };
     // quadtree / describe of the frames [b0, b0 + nb)
     const size_t qtPerFrame = B > 0 ? quadtree_table_scratch_bytes(G, 1) : 0;
     auto quadtree_part = [&](hipStream_t st, int b0, int nb) {
-        launch_quadtree(st, G, c->d_cand + (size_t)b0 * G.totalCands, c->d_cellCnt + (size_t)b0 * G.totalCells,
-                        c->d_pts + (size_t)b0 * G.totalPts, c->d_pnode + (size_t)b0 * G.totalPts,
-                        c->d_lvlCandCnt + (size_t)b0 * ORBHIP_MAX_LEVELS, c->d_lvlKp + (size_t)b0 * G.totalKps,
-                        c->d_lvlKpCnt + (size_t)b0 * ORBHIP_MAX_LEVELS, nb, c->d_qtTables ? c->d_qtTables + (size_t)b0 * qtPerFrame : nullptr);
+        launch_quadtree(st, G, c->d_cand.as<uint32_t>() + (size_t)b0 * G.totalCands,
+                        c->d_cellCnt.as<uint16_t>() + (size_t)b0 * G.totalCells,
+                        c->d_pts.as<uint32_t>() + (size_t)b0 * G.totalPts, c->d_pnode.as<uint32_t>() + (size_t)b0 * G.totalPts,
+                        c->d_lvlCandCnt.as<int32_t>() + (size_t)b0 * ORBHIP_MAX_LEVELS,
+                        c->d_lvlKp.as<uint32_t>() + (size_t)b0 * G.totalKps,
+                        c->d_lvlKpCnt.as<int32_t>() + (size_t)b0 * ORBHIP_MAX_LEVELS, nb,
+                        c->d_qtTables ? c->d_qtTables.as<uint8_t>() + (size_t)b0 * qtPerFrame : nullptr);
     };
     auto describe_part = [&](hipStream_t st, int b0, int nb) {
         if (fusedDescribe) {
-            launch_describe_blur(st, G, lvl0 + (size_t)b0 * frame0, stride0, frame0, c->d_pyr + (size_t)b0 * c->pyrFrameBytes,
-                                 c->pyrFrameBytes, c->d_lvlKp + (size_t)b0 * G.totalKps, c->d_lvlKpCnt + (size_t)b0 * ORBHIP_MAX_LEVELS,
-                                 c->d_lvlAngle + (size_t)b0 * G.totalKps, d_kps + (size_t)b0 * cap, d_desc + (size_t)b0 * cap * 32,
+            launch_describe_blur(st, G, lvl0 + (size_t)b0 * frame0, stride0, frame0,
+                                 c->d_pyr.as<uint8_t>() + (size_t)b0 * c->pyrFrameBytes,
+                                 c->pyrFrameBytes, c->d_lvlKp.as<uint32_t>() + (size_t)b0 * G.totalKps,
+                                 c->d_lvlKpCnt.as<int32_t>() + (size_t)b0 * ORBHIP_MAX_LEVELS,
+                                 c->d_lvlAngle.as<float>() + (size_t)b0 * G.totalKps, d_kps + (size_t)b0 * cap,
+                                 d_desc + (size_t)b0 * cap * 32,
                                  d_counts + b0, cap, nb);
             return;
         }
-        launch_describe(st, G, lvl0 + (size_t)b0 * frame0, stride0, frame0, c->d_pyr + (size_t)b0 * c->pyrFrameBytes, c->pyrFrameBytes,
-                        c->d_blur + (size_t)b0 * blurFrame, blurFrame, c->d_lvlKp + (size_t)b0 * G.totalKps,
-                        c->d_lvlKpCnt + (size_t)b0 * ORBHIP_MAX_LEVELS, c->d_lvlAngle + (size_t)b0 * G.totalKps, d_kps + (size_t)b0 * cap,
+        launch_describe(st, G, lvl0 + (size_t)b0 * frame0, stride0, frame0,
+                        c->d_pyr.as<uint8_t>() + (size_t)b0 * c->pyrFrameBytes, c->pyrFrameBytes,
+                        c->d_blur.as<uint8_t>() + (size_t)b0 * blurFrame, blurFrame,
+                        c->d_lvlKp.as<uint32_t>() + (size_t)b0 * G.totalKps,
+                        c->d_lvlKpCnt.as<int32_t>() + (size_t)b0 * ORBHIP_MAX_LEVELS,
+                        c->d_lvlAngle.as<float>() + (size_t)b0 * G.totalKps, d_kps + (size_t)b0 * cap,
                         d_desc + (size_t)b0 * cap * 32, d_counts + b0, cap, nb, B < 8 ? c->describeMirror : 0);
     };
     if (B >= 8)
-        launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_fastTiles, c->nFastTilesBatch, c->d_cand,
-                    c->d_cellCnt, B, c->nFastTilesTall);
+        launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr.as<uint8_t>(), c->pyrFrameBytes, c->d_fastTiles.as<FastTile>(),
+                    c->nFastTilesBatch, c->d_cand.as<uint32_t>(),
+                    c->d_cellCnt.as<uint16_t>(), B, c->nFastTilesTall);
     else
-        launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr, c->pyrFrameBytes, c->d_fastTiles + c->nFastTilesBatch,
-                    (int)c->fastTiles.size() - c->nFastTilesBatch, c->d_cand, c->d_cellCnt, B);
+        launch_fast(s, G, lvl0, stride0, frame0, c->d_pyr.as<uint8_t>(), c->pyrFrameBytes,
+                    c->d_fastTiles.as<FastTile>() + c->nFastTilesBatch,
+                    (int)c->fastTiles.size() - c->nFastTilesBatch, c->d_cand.as<uint32_t>(), c->d_cellCnt.as<uint16_t>(), B);
     if (evFast) HIPCHK(c, hipEventRecord(c->ev[2], s));
     const int nA = B >= 16 ? B / 2 : B, nB = B - nA;   // the two parts of the quadtree / describe
     if (B < 8) {
@@ -414,7 +419,7 @@ int orb_run_pipeline(orbhip_ctx *c, const uint8_t *lvl0, int stride0, size_t fra
     if (pyrFork)
         HIPCHK(c, hipStreamWaitEvent(s, c->evp[1], 0));
     else if (h_pyr_dst && G.nlevels > 1 && !chained)
-        HIPCHK(c, hipMemcpyAsync(h_pyr_dst, c->d_pyr, (size_t)B * c->pyrFrameBytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(h_pyr_dst, c->d_pyr.as<uint8_t>(), (size_t)B * c->pyrFrameBytes, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipGetLastError());
     if (!c->capturing) {
         c->haveStageEvents = ev;
@@ -476,23 +481,17 @@ extern "C" int orbhip_extract_batch_device(orbhip_ctx *c, const void *d_imgs, in
     const int s0 = (int)align_up((size_t)w, 64);
     if ((rc = orb_configure(c, w, h, s0, B))) return rc;
     for (int b = 0; b < B; b++)
-        HIPCHK(c, hipMemcpy2DAsync(c->d_lvl0 + (size_t)b * c->lvl0FrameBytes, s0,
+        HIPCHK(c, hipMemcpy2DAsync(c->d_lvl0.as<uint8_t>() + (size_t)b * c->lvl0FrameBytes, s0,
                                    (const uint8_t *)d_imgs + (size_t)b * frame_stride, stride, w, h,
                                    hipMemcpyDeviceToDevice, c->stream));
-    return orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)d_kps, (uint8_t *)d_desc,
+    return orb_run_pipeline(c, c->d_lvl0.as<uint8_t>(), s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)d_kps, (uint8_t *)d_desc,
                         (int32_t *)d_counts, cap);
 }
 
 int orb_host_stage(orbhip_ctx *c, size_t bytes)
 {
-    if (bytes <= c->h_stage_bytes) return ORBHIP_OK;
-    if (c->h_stage) HIPCHK(c, hipHostFree(c->h_stage));
-    c->h_stage = nullptr;
-    c->h_stage_bytes = 0;
-    void *p = nullptr;
-    HIPCHK(c, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-    c->h_stage = (uint8_t *)p;
-    c->h_stage_bytes = bytes;
+    if (bytes <= c->h_stage.bytes()) return ORBHIP_OK;
+    HIPCHK(c, c->h_stage.grow(bytes));
     return ORBHIP_OK;
 }
 
@@ -503,105 +502,94 @@ int orb_host_pyr_stage(orbhip_ctx *c, int B, uint8_t **dst)
     c->h_pyr_B = 0;
     if (!c->hostPyr || c->G.nlevels < 2) return ORBHIP_OK;
     const size_t bytes = (size_t)B * c->pyrFrameBytes;
-    if (bytes > c->h_pyr_bytes) {
-        if (c->h_pyr) HIPCHK(c, hipHostFree(c->h_pyr));
-        c->h_pyr = nullptr;
-        c->h_pyr_bytes = 0;
-        void *p = nullptr;
-        HIPCHK(c, hipHostMalloc(&p, bytes, hipHostMallocDefault));
-        c->h_pyr = (uint8_t *)p;
-        c->h_pyr_bytes = bytes;
-    }
-    *dst = c->h_pyr;
+    if (bytes > c->h_pyr.bytes()) HIPCHK(c, c->h_pyr.grow(bytes));
+    *dst = c->h_pyr.as<uint8_t>();
     return ORBHIP_OK;
 }
 
-void orb_graph_release(orbhip_ctx *c)
+// the single-frame graphs hold h_in's address: the context's (and `also`) go when it is replaced
+int orb_host_in_stage(orbhip_ctx *c, size_t bytes, OrbGraph *also)
 {
-    if (c->g_exec) (void)hipGraphExecDestroy(c->g_exec);
-    if (c->g_graph) (void)hipGraphDestroy(c->g_graph);
-    c->g_exec = nullptr;
-    c->g_graph = nullptr;
-    c->g_w = c->g_h = c->g_B = 0;
+    if (bytes <= c->h_in.bytes()) return ORBHIP_OK;
+    c->graph.release();
+    if (also) also->release();
+    HIPCHK(c, c->h_in.grow(bytes));
+    return ORBHIP_OK;
+}
+
+// The chain `enqueue` puts on c->stream (its copy-in first) as one hipGraph launch: captured again when the caller's replay key
+// or the context's allocation generation has changed.  The first call after a capture and every 256th one run the chain
+// eagerly instead: that refreshes the stage times behind GetTimeOfComputePyramid / ...KeyPointsOctTree / ...Descriptor
+// (include/ORBextractor.h:51-53), which a replay does not record.
+int orb_graph_run(orbhip_ctx *c, OrbGraph &g, const void *key, size_t keyBytes, const std::function<int()> &enqueue,
+                  const char *failMsg)
+{
+    const bool same = g.exec && g.gen == c->allocGen && g.key.size() == keyBytes && memcmp(g.key.data(), key, keyBytes) == 0;
+    if (!same) {
+        g.release();
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream2));
+        c->capturing = true;
+        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue();
+        hipGraph_t graph = nullptr;
+        const hipError_t e = hipStreamEndCapture(c->stream, &graph);
+        c->capturing = false;
+        if (rc != ORBHIP_OK || e != hipSuccess || !graph) {
+            if (graph) (void)hipGraphDestroy(graph);
+            (void)hipGetLastError();
+            // (a refusal of the chain itself -- ORBHIP_E_SIZE from the grid kernel's limit -- keeps its own code)
+            return fail(c, rc != ORBHIP_OK ? rc : ORBHIP_E_HIP,
+                        std::string(failMsg) + (rc != ORBHIP_OK ? c->err : std::string(hipGetErrorString(e))));
+        }
+        g.graph = graph;
+        HIPCHK(c, hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0));
+        g.key.assign((const uint8_t *)key, (const uint8_t *)key + keyBytes);
+        g.gen = c->allocGen;
+        g.calls = 0;
+    }
+    if ((g.calls++ & 255u) == 0) return enqueue();
+    HIPCHK(c, hipGraphLaunch(g.exec, c->stream));
+    return ORBHIP_OK;
 }
 
 // A frame or two through host pointers (how Tracking.cc calls the extractor, src/Frame.cc:591-597): the whole chain -- copy
 // in, seven resize launches, FAST, quadtree, blur, describe, copy out -- is ONE hipGraph launch.  Issued one by one the twelve
 // launches cost the host ~3.5 us each and the device waits for them; the graph is captured from the very same call sequence
 // (run_pipeline) at the first call of a geometry and replayed afterwards.  ORBHIP_NO_GRAPH=1 keeps the eager sequence.
-static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int s0, size_t kbytes,
-                               size_t dbytes, size_t cbytes, size_t koff, size_t doff, size_t coff, int dcap)
+static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int s0, size_t cbytes,
+                               size_t koff, size_t doff, size_t coff, int dcap)
 {
     const size_t inBytes = (size_t)B * c->lvl0FrameBytes;
-    if (inBytes > c->h_in_bytes) {
-        orb_graph_release(c);
-        if (c->h_in) HIPCHK(c, hipHostFree(c->h_in));
-        c->h_in = nullptr;
-        c->h_in_bytes = 0;
-        void *p = nullptr;
-        HIPCHK(c, hipHostMalloc(&p, inBytes, hipHostMallocDefault));
-        c->h_in = (uint8_t *)p;
-        c->h_in_bytes = inBytes;
-    }
     int rc;
+    if ((rc = orb_host_in_stage(c, inBytes))) return rc;
     if ((rc = orb_host_stage(c, coff + align_up(cbytes, 256)))) return rc;
     uint8_t *hpyr = nullptr;
     if ((rc = orb_host_pyr_stage(c, B, &hpyr))) return rc;
     c->h_in_valid = false;
     for (int b = 0; b < B; b++) {
         if (!imgs[b]) return fail(c, ORBHIP_E_ARG, "orbhip_extract_batch: null image");
-        uint8_t *dst = c->h_in + (size_t)b * c->lvl0FrameBytes;
+        uint8_t *dst = c->h_in.as<uint8_t>() + (size_t)b * c->lvl0FrameBytes;
         if (stride == s0)
             memcpy(dst, imgs[b], (size_t)s0 * (h - 1) + w);
         else
             for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * s0, imgs[b] + (size_t)y * stride, (size_t)w);
     }
-    const void *key[5] = {c->d_lvl0, c->d_kps, c->h_in, c->h_stage, hpyr};
-    const bool same = c->g_exec && c->g_w == w && c->g_h == h && c->g_B == B && c->g_gen == c->allocGen &&
-                      memcmp(key, c->g_key, sizeof(key)) == 0;
-    if (!same) {
-        orb_graph_release(c);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        c->capturing = true;
-        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        // the describe kernel writes keypoints, descriptors and counts straight into the page-locked result block (posted PCIe
-        // writes of a few dozen KB that overlap the kernel): no copy node behind it -- that node started 8 us after describe ended
-        uint8_t *out = c->h_stage;
-        hipError_t e = hipMemcpyAsync(c->d_lvl0, c->h_in, inBytes, hipMemcpyHostToDevice, c->stream);
-        rc = e == hipSuccess ? orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
-                                            (int32_t *)(out + coff), dcap, hpyr)
-                             : ORBHIP_E_HIP;
-        hipGraph_t g = nullptr;
-        const hipError_t e2 = hipStreamEndCapture(c->stream, &g);
-        c->capturing = false;
-        if (rc != ORBHIP_OK || e != hipSuccess || e2 != hipSuccess || !g) {
-            if (g) (void)hipGraphDestroy(g);
-            const std::string inner = rc != ORBHIP_OK ? c->err : std::string();   // (what a call inside the captured chain reported)
-            return fail(c, ORBHIP_E_HIP, std::string("graph capture of the single-frame chain failed: ") +
-                                             hipGetErrorString(e != hipSuccess ? e : e2) + (inner.empty() ? "" : " [" + inner + "]"));
-        }
-        c->g_graph = g;
-        HIPCHK(c, hipGraphInstantiate(&c->g_exec, g, nullptr, nullptr, 0));
-        c->g_w = w; c->g_h = h; c->g_B = B;
-        memcpy(c->g_key, key, sizeof(key));
-        c->g_gen = c->allocGen;
-        c->g_calls = 0;
-    }
-    if ((c->g_calls++ & 255u) == 0) {
-        // the first call of a geometry and every 256th one run the same chain eagerly: that refreshes the stage times behind
-        // GetTimeOfComputePyramid / ...KeyPointsOctTree / ...Descriptor (include/ORBextractor.h:51-53)
-        uint8_t *out = c->h_stage;
-        HIPCHK(c, hipMemcpyAsync(c->d_lvl0, c->h_in, inBytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
-                               (int32_t *)(out + coff), dcap, hpyr)))
-            return rc;
-    } else {
-        HIPCHK(c, hipGraphLaunch(c->g_exec, c->stream));
-    }
+    const uintptr_t key[8] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)B, (uintptr_t)c->d_lvl0.as<void>(),
+                              (uintptr_t)c->d_kps.as<void>(),
+                              (uintptr_t)c->h_in.as<void>(), (uintptr_t)c->h_stage.as<void>(), (uintptr_t)hpyr};
+    // the describe kernel writes keypoints, descriptors and counts straight into the page-locked result block (posted PCIe
+    // writes of a few dozen KB that overlap the kernel): no copy node behind it -- that node started 8 us after describe ended
+    auto enqueue = [&]() -> int {
+        uint8_t *out = c->h_stage.as<uint8_t>();
+        HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), inBytes, hipMemcpyHostToDevice, c->stream));
+        return orb_run_pipeline(c, c->d_lvl0.as<uint8_t>(), s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
+                                (int32_t *)(out + coff), dcap, hpyr);
+    };
+    if ((rc = orb_graph_run(c, c->graph, key, sizeof(key), enqueue, "graph capture of the single-frame chain failed: "))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->h_in_valid = true;
     c->h_pyr_B = hpyr ? B : 0;
-    (void)kbytes; (void)dbytes;
     return ORBHIP_OK;
 }
 
@@ -620,33 +608,35 @@ extern "C" int orbhip_extract_batch(orbhip_ctx *c, const uint8_t *const *imgs, i
     // most of a single frame's overhead); the n[b] valid entries are then copied out on the host
     const size_t kbytes = (size_t)B * dcap * sizeof(orbhip_keypoint), dbytes = (size_t)B * dcap * 32, cbytes = (size_t)B * 4;
     const size_t koff = 0, doff = align_up(kbytes, 256), coff = doff + align_up(dbytes, 256);
-    uint8_t *blk = reinterpret_cast<uint8_t *>(c->d_kps);
+    uint8_t *blk = reinterpret_cast<uint8_t *>(c->d_kps.as<uint8_t>());
     static const bool noGraph = ORB_SWITCH("NO_GRAPH", 0) != 0;
     if (B < 8 && !noGraph) {
-        if ((rc = extract_small_graph(c, imgs, B, w, h, stride, s0, kbytes, dbytes, cbytes, koff, doff, coff, dcap))) return rc;
+        if ((rc = extract_small_graph(c, imgs, B, w, h, stride, s0, cbytes, koff, doff, coff, dcap))) return rc;
     } else {
         for (int b = 0; b < B; b++) {
             if (!imgs[b]) return fail(c, ORBHIP_E_ARG, "orbhip_extract_batch: null image");
-            HIPCHK(c, hipMemcpy2DAsync(c->d_lvl0 + (size_t)b * c->lvl0FrameBytes, s0, imgs[b], stride, w, h,
+            HIPCHK(c, hipMemcpy2DAsync(c->d_lvl0.as<uint8_t>() + (size_t)b * c->lvl0FrameBytes, s0, imgs[b], stride, w, h,
                                        hipMemcpyHostToDevice, c->stream));
         }
         uint8_t *hpyr = nullptr;
         if ((rc = orb_host_pyr_stage(c, B, &hpyr))) return rc;
         c->h_in_valid = false;
-        if ((rc = orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(blk + koff), blk + doff,
+        if ((rc = orb_run_pipeline(c, c->d_lvl0.as<uint8_t>(), s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(blk + koff),
+                                   blk + doff,
                                (int32_t *)(blk + coff), dcap, hpyr)))
             return rc;
         if ((rc = orb_host_stage(c, coff + align_up(cbytes, 256)))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->h_stage, blk, coff + cbytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_stage.as<uint8_t>(), blk, coff + cbytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->h_pyr_B = hpyr ? B : 0;
     }
-    memcpy(n_out, c->h_stage + coff, cbytes);
+    memcpy(n_out, c->h_stage.as<uint8_t>() + coff, cbytes);
     for (int b = 0; b < B; b++) {
         const int n = n_out[b];
         if (n > cap || n > dcap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_extract_batch: output capacity too small");
-        memcpy(kps + (size_t)b * cap, c->h_stage + koff + (size_t)b * dcap * sizeof(orbhip_keypoint), (size_t)n * sizeof(orbhip_keypoint));
-        memcpy(desc + (size_t)b * cap * 32, c->h_stage + doff + (size_t)b * dcap * 32, (size_t)n * 32);
+        memcpy(kps + (size_t)b * cap, c->h_stage.as<uint8_t>() + koff + (size_t)b * dcap * sizeof(orbhip_keypoint),
+               (size_t)n * sizeof(orbhip_keypoint));
+        memcpy(desc + (size_t)b * cap * 32, c->h_stage.as<uint8_t>() + doff + (size_t)b * dcap * 32, (size_t)n * 32);
     }
     return ORBHIP_OK;
 }
@@ -688,7 +678,7 @@ extern "C" int orbhip_get_pyramid_level(orbhip_ctx *c, int frame, int level, uin
     HIPCHK(c, orb_enter(c));
     if (level == 0)
         return copy_level(c, c->last_lvl0 + (size_t)frame * c->last_frame0, c->last_stride0, L.w, L.h, dst, dst_stride);
-    return copy_level(c, c->d_pyr + (size_t)frame * c->pyrFrameBytes + L.imgOff, L.stride, L.w, L.h, dst, dst_stride);
+    return copy_level(c, c->d_pyr.as<uint8_t>() + (size_t)frame * c->pyrFrameBytes + L.imgOff, L.stride, L.w, L.h, dst, dst_stride);
 }
 
 extern "C" int orbhip_set_host_pyramid(orbhip_ctx *c, int on)
@@ -708,15 +698,15 @@ extern "C" int orbhip_host_pyramid_level(orbhip_ctx *c, int frame, int level, co
     if (h) *h = L.h;
     if (level == 0) {
         // the pinned copy of the caller's frame that the single-frame path uploads from (rows last_stride0 apart)
-        if (!c->h_in_valid || frame >= c->last_B || c->last_lvl0 != c->d_lvl0)
+        if (!c->h_in_valid || frame >= c->last_B || c->last_lvl0 != c->d_lvl0.as<uint8_t>())
             return fail(c, ORBHIP_E_ARG, "orbhip_host_pyramid_level: level 0 is not staged on the host for this call (use the caller's image)");
-        *ptr = c->h_in + (size_t)frame * c->lvl0FrameBytes;
+        *ptr = c->h_in.as<uint8_t>() + (size_t)frame * c->lvl0FrameBytes;
         *stride = c->last_stride0;
         return ORBHIP_OK;
     }
     if (frame >= c->h_pyr_B)
         return fail(c, ORBHIP_E_ARG, "orbhip_host_pyramid_level: no host pyramid for this frame (orbhip_set_host_pyramid before orbhip_extract*)");
-    *ptr = c->h_pyr + (size_t)frame * c->pyrFrameBytes + L.imgOff;
+    *ptr = c->h_pyr.as<uint8_t>() + (size_t)frame * c->pyrFrameBytes + L.imgOff;
     *stride = L.stride;
     return ORBHIP_OK;
 }
@@ -734,12 +724,13 @@ extern "C" int orbhip_debug_get_blurred_level(orbhip_ctx *c, int frame, int leve
     const size_t bf = c->lvl0FrameBytes + c->pyrFrameBytes;
     if (!c->blurValid) {
         // the last batch ran k_describe_blur and never built the blurred pyramid: k_blur on the same levels, now
-        launch_blur(c->stream, c->G, c->last_lvl0, c->last_stride0, c->last_frame0, c->d_pyr, c->pyrFrameBytes, c->d_blur, bf,
-                    c->d_blurTiles, (int)c->blurTiles.size(), c->d_blurBands, c->last_B);
+        launch_blur(c->stream, c->G, c->last_lvl0, c->last_stride0, c->last_frame0, c->d_pyr.as<uint8_t>(), c->pyrFrameBytes,
+                    c->d_blur.as<uint8_t>(), bf,
+                    c->d_blurTiles.as<BlurTile>(), (int)c->blurTiles.size(), c->d_blurBands.as<uint32_t>(), c->last_B);
         HIPCHK(c, hipGetLastError());
         c->blurValid = true;
     }
-    const uint8_t *src = c->d_blur + (size_t)frame * bf + (level == 0 ? 0 : c->G.boff1 + L.imgOff);
+    const uint8_t *src = c->d_blur.as<uint8_t>() + (size_t)frame * bf + (level == 0 ? 0 : c->G.boff1 + L.imgOff);
     return copy_level(c, src, level == 0 ? c->G.bstride0 : L.stride, L.w, L.h, dst, dst_stride);
 }
 
@@ -754,9 +745,11 @@ extern "C" int orbhip_debug_get_candidates(orbhip_ctx *c, int frame, int level, 
     const int ncells = L.nCols * L.nRows;
     std::vector<uint16_t> cnt(ncells);
     std::vector<uint32_t> slots((size_t)L.ptCap);
-    HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_cellCnt + (size_t)frame * G.totalCells + L.cellBase, (size_t)ncells * 2,
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), c->d_cellCnt.as<uint16_t>() + (size_t)frame * G.totalCells + L.cellBase,
+                             (size_t)ncells * 2,
                              hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(slots.data(), c->d_cand + (size_t)frame * G.totalCands + L.candBase, (size_t)L.ptCap * 4,
+    HIPCHK(c, hipMemcpyAsync(slots.data(), c->d_cand.as<uint32_t>() + (size_t)frame * G.totalCands + L.candBase,
+                             (size_t)L.ptCap * 4,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int n = 0;
@@ -784,7 +777,8 @@ extern "C" int orbhip_debug_get_level_keypoints(orbhip_ctx *c, int frame, int le
     const OrbLevels &G = c->G;
     const OrbLevel &L = G.lv[level];
     int32_t cnts[ORBHIP_MAX_LEVELS];
-    HIPCHK(c, hipMemcpyAsync(cnts, c->d_lvlKpCnt + (size_t)frame * ORBHIP_MAX_LEVELS, sizeof(cnts), hipMemcpyDeviceToHost,
+    HIPCHK(c, hipMemcpyAsync(cnts, c->d_lvlKpCnt.as<int32_t>() + (size_t)frame * ORBHIP_MAX_LEVELS, sizeof(cnts),
+                             hipMemcpyDeviceToHost,
                              c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int n = cnts[level];
@@ -793,9 +787,9 @@ extern "C" int orbhip_debug_get_level_keypoints(orbhip_ctx *c, int frame, int le
     if (n > cap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_debug_get_level_keypoints: capacity");
     std::vector<uint32_t> pk(n);
     std::vector<float> ang(n);
-    HIPCHK(c, hipMemcpyAsync(pk.data(), c->d_lvlKp + (size_t)frame * G.totalKps + L.kpBase, (size_t)n * 4,
+    HIPCHK(c, hipMemcpyAsync(pk.data(), c->d_lvlKp.as<uint32_t>() + (size_t)frame * G.totalKps + L.kpBase, (size_t)n * 4,
                              hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(ang.data(), c->d_lvlAngle + (size_t)frame * G.totalKps + L.kpBase, (size_t)n * 4,
+    HIPCHK(c, hipMemcpyAsync(ang.data(), c->d_lvlAngle.as<float>() + (size_t)frame * G.totalKps + L.kpBase, (size_t)n * 4,
                              hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; i++) {

@@ -22,9 +22,8 @@
 #include <vector>
 
 struct OrbFrameBuild {
-    uint8_t *d_blk = nullptr;   // packed results, device
-    uint8_t *h_blk = nullptr;   // page-locked twin
-    size_t bytes = 0;
+    OrbBlock d_blk;                    // packed results, device
+    OrbBlock h_blk{OrbBlock::Host};    // page-locked twin
     int dcap = 0;
     // offsets inside the block; [oU, setEnd) has the layout of a resident set's block (api_sets.hip)
     size_t oU = 0, oD = 0, oC = 0, oG = 0, oE = 0, setEnd = 0, oK = 0, oW = 0, oT = 0, oN = 0;
@@ -34,37 +33,21 @@ struct OrbFrameBuild {
     // second copier: the build then waited for the last copy only.)
     std::mutex busyMu;
     std::vector<hipEvent_t> busyEvents, freeEvents;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    // replay key
-    int w = 0, h = 0;
-    orbhip_frame_params fp;
-    const void *key[7] = {};
-    unsigned long gen = 0;
-    unsigned calls = 0;
+    OrbGraph graph;
     // the frame whose results the block holds
     bool valid = false, undist = false, grid = false, bow = false;
     int n = 0;
+    orbhip_frame_params fp;
     uint64_t fingerprint = 0;
 };
 
 static OrbFrameBuild *fb_of(orbhip_ctx *c) { return static_cast<OrbFrameBuild *>(c->frameBuild); }
 
-static void fb_graph_release(OrbFrameBuild *F)
-{
-    if (F->exec) (void)hipGraphExecDestroy(F->exec);
-    if (F->graph) (void)hipGraphDestroy(F->graph);
-    F->exec = nullptr;
-    F->graph = nullptr;
-}
-
 void orb_frame_release(orbhip_ctx *c)
 {
     OrbFrameBuild *F = fb_of(c);
     if (!F) return;
-    fb_graph_release(F);
-    if (F->d_blk) (void)hipFree(F->d_blk);
-    if (F->h_blk) (void)hipHostFree(F->h_blk);
+    F->graph.release();
     for (hipEvent_t e : F->busyEvents) (void)hipEventSynchronize(e);
     for (hipEvent_t e : F->busyEvents) (void)hipEventDestroy(e);
     for (hipEvent_t e : F->freeEvents) (void)hipEventDestroy(e);
@@ -111,7 +94,7 @@ static int fb_enqueue(orbhip_ctx *c, OrbFrameBuild *F, const orbhip_frame_params
     // Every kernel stores its results twice: into the device block (read by the kernels behind it, and by
     // orbhip_set_put_from_frame later) and into its page-locked twin -- posted PCIe writes of a few dozen KB per kernel that
     // overlap the kernels; no copy command follows (a copy node behind the last kernel started ~8 us after it ended).
-    uint8_t *B = F->d_blk, *H = F->h_blk;
+    uint8_t *B = F->d_blk.as<uint8_t>(), *H = F->h_blk.as<uint8_t>();
     orbhip_keypoint *dK = (orbhip_keypoint *)(B + (undist ? F->oK : F->oU));
     orbhip_keypoint *dU = (orbhip_keypoint *)(B + F->oU);
     uint8_t *dD = B + F->oD;
@@ -120,7 +103,7 @@ static int fb_enqueue(orbhip_ctx *c, OrbFrameBuild *F, const orbhip_frame_params
     int rc;
     if ((rc = orb_host_pyr_stage(c, 1, &hpyr))) return rc;
     c->describeMirror = (long long)(H - B);
-    rc = orb_run_pipeline(c, c->d_lvl0, s0, c->lvl0FrameBytes, 1, dK, dD, dC, F->dcap, hpyr);
+    rc = orb_run_pipeline(c, c->d_lvl0.as<uint8_t>(), s0, c->lvl0FrameBytes, 1, dK, dD, dC, F->dcap, hpyr);
     c->describeMirror = 0;
     if (rc) return rc;
     if (bow) {
@@ -172,10 +155,9 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
     const int dcap = (int)c->cap_out;
     if (F->dcap != dcap || !F->d_blk) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        fb_graph_release(F);
-        if (F->d_blk) HIPCHK(c, hipFree(F->d_blk));
-        if (F->h_blk) HIPCHK(c, hipHostFree(F->h_blk));
-        F->d_blk = F->h_blk = nullptr;
+        F->graph.release();
+        F->d_blk.reset();
+        F->h_blk.reset();
         size_t o = 0;
         auto carve = [&](size_t bytes) { const size_t at = o; o = align_up(o + bytes, 256); return at; };
         F->oU = carve((size_t)dcap * sizeof(orbhip_keypoint));
@@ -188,35 +170,21 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
         F->oW = carve((size_t)dcap * 4);
         F->oT = carve((size_t)dcap * 4);
         F->oN = carve((size_t)dcap * 4);
-        F->bytes = o;
-        void *p = nullptr;
-        HIPCHK(c, hipMalloc(&p, o));
-        F->d_blk = (uint8_t *)p;
-        HIPCHK(c, hipHostMalloc(&p, o, hipHostMallocDefault));
-        F->h_blk = (uint8_t *)p;
+        HIPCHK(c, F->d_blk.grow(o));
+        HIPCHK(c, F->h_blk.grow(o));
         F->dcap = dcap;
         F->valid = false;
     }
     // page-locked input staging (shared with orbhip_extract's graph)
-    if (c->lvl0FrameBytes > c->h_in_bytes) {
-        orb_graph_release(c);
-        fb_graph_release(F);
-        if (c->h_in) HIPCHK(c, hipHostFree(c->h_in));
-        c->h_in = nullptr;
-        c->h_in_bytes = 0;
-        void *p = nullptr;
-        HIPCHK(c, hipHostMalloc(&p, c->lvl0FrameBytes, hipHostMallocDefault));
-        c->h_in = (uint8_t *)p;
-        c->h_in_bytes = c->lvl0FrameBytes;
-    }
+    if ((rc = orb_host_in_stage(c, c->lvl0FrameBytes, &F->graph))) return rc;
     uint8_t *hpyr = nullptr;
     if ((rc = orb_host_pyr_stage(c, 1, &hpyr))) return rc;
     c->h_in_valid = false;
     F->valid = false;
     if (stride == s0)
-        memcpy(c->h_in, img, (size_t)s0 * (h - 1) + w);
+        memcpy(c->h_in.as<uint8_t>(), img, (size_t)s0 * (h - 1) + w);
     else
-        for (int y = 0; y < h; y++) memcpy(c->h_in + (size_t)y * s0, img + (size_t)y * stride, (size_t)w);
+        for (int y = 0; y < h; y++) memcpy(c->h_in.as<uint8_t>() + (size_t)y * s0, img + (size_t)y * stride, (size_t)w);
     // a context that is still copying the last frame's block into a resident set (orbhip_set_put_from_frame) goes first
     {
         std::vector<hipEvent_t> pending;
@@ -234,49 +202,29 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
         }
         HIPCHK(c, e);
     }
-    const void *key[7] = {c->d_lvl0, F->d_blk, c->h_in, F->h_blk, hpyr, c->voc.desc, (const void *)(uintptr_t)c->voc.gen};
-    const bool same = F->exec && F->w == w && F->h == h && F->gen == c->allocGen && memcmp(key, F->key, sizeof(key)) == 0 &&
-                      memcmp(&F->fp, fp, sizeof(*fp)) == 0;
+    auto enqueue = [&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), c->lvl0FrameBytes, hipMemcpyHostToDevice,
+                                 c->stream));
+        return fb_enqueue(c, F, *fp, s0, undist, grid, bow);
+    };
     static const bool noGraph = ORB_SWITCH("NO_GRAPH", 0) != 0;
-    if (!same && !noGraph) {
-        fb_graph_release(F);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream2));
-        c->capturing = true;
-        HIPCHK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        hipError_t e = hipMemcpyAsync(c->d_lvl0, c->h_in, c->lvl0FrameBytes, hipMemcpyHostToDevice, c->stream);
-        rc = e == hipSuccess ? fb_enqueue(c, F, *fp, s0, undist, grid, bow) : ORBHIP_E_HIP;
-        hipGraph_t g = nullptr;
-        const hipError_t e2 = hipStreamEndCapture(c->stream, &g);
-        c->capturing = false;
-        if (rc != ORBHIP_OK || e != hipSuccess || e2 != hipSuccess || !g) {
-            if (g) (void)hipGraphDestroy(g);
-            (void)hipGetLastError();
-            // (a refusal of fb_enqueue itself -- ORBHIP_E_SIZE from the grid kernel's limit -- keeps its own code)
-            return fail(c, rc != ORBHIP_OK ? rc : ORBHIP_E_HIP, std::string("orbhip_frame_build: graph capture failed: ") +
-                                             (rc != ORBHIP_OK ? c->err : std::string(hipGetErrorString(e != hipSuccess ? e : e2))));
-        }
-        F->graph = g;
-        HIPCHK(c, hipGraphInstantiate(&F->exec, g, nullptr, nullptr, 0));
-        F->w = w;
-        F->h = h;
-        F->fp = *fp;
-        memcpy(F->key, key, sizeof(key));
-        F->gen = c->allocGen;
-        F->calls = 0;
-    }
-    if (noGraph || (F->calls++ & 255u) == 0) {
-        // eagerly: the first call of a geometry and every 256th one refresh the stage times behind GetTimeOfComputePyramid / ...
-        HIPCHK(c, hipMemcpyAsync(c->d_lvl0, c->h_in, c->lvl0FrameBytes, hipMemcpyHostToDevice, c->stream));
-        if ((rc = fb_enqueue(c, F, *fp, s0, undist, grid, bow))) return rc;
+    if (noGraph) {
+        rc = enqueue();
     } else {
-        HIPCHK(c, hipGraphLaunch(F->exec, c->stream));
+        uint8_t key[9 * sizeof(uintptr_t) + sizeof(*fp)];
+        const uintptr_t k[9] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)c->d_lvl0.as<void>(), (uintptr_t)F->d_blk.as<void>(),
+                                (uintptr_t)c->h_in.as<void>(), (uintptr_t)F->h_blk.as<void>(), (uintptr_t)hpyr,
+                                (uintptr_t)c->voc.desc, (uintptr_t)c->voc.gen};
+        memcpy(key, k, sizeof(k));
+        memcpy(key + sizeof(k), fp, sizeof(*fp));
+        rc = orb_graph_run(c, F->graph, key, sizeof(key), enqueue, "orbhip_frame_build: graph capture failed: ");
     }
+    if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->h_in_valid = true;
     c->h_pyr_B = hpyr ? 1 : 0;
     // results: the packed block -> the caller's arrays
-    const uint8_t *H = F->h_blk;
+    const uint8_t *H = F->h_blk.as<uint8_t>();
     const int n = *(const int32_t *)(H + F->oC);
     *n_out = n;
     if (n < 0 || n > cap || n > dcap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_frame_build: output capacity too small");
@@ -297,6 +245,7 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
     F->grid = grid;
     F->bow = bow;
     F->n = n;
+    F->fp = *fp;
     F->fingerprint = orbhip_set_fingerprint(kps_un, desc, n);
     return ORBHIP_OK;
 }
@@ -314,7 +263,7 @@ int orb_frame_block(orbhip_ctx *src, const uint8_t **d_blk, size_t *setBytes, si
 {
     OrbFrameBuild *F = src ? fb_of(src) : nullptr;
     if (!F || !F->valid || F->n <= 0) return ORBHIP_E_ARG;
-    *d_blk = F->d_blk + F->oU;
+    *d_blk = F->d_blk.as<uint8_t>() + F->oU;
     *setBytes = F->setEnd - F->oU;
     off[0] = 0;
     off[1] = F->oD - F->oU;
@@ -325,8 +274,8 @@ int orb_frame_block(orbhip_ctx *src, const uint8_t **d_blk, size_t *setBytes, si
     *dcap = F->dcap;
     *grid = F->grid;
     gp[0] = F->fp.min_x; gp[1] = F->fp.min_y; gp[2] = F->fp.inv_w; gp[3] = F->fp.inv_h;
-    *h_kps_un = (const orbhip_keypoint *)(F->h_blk + F->oU);
-    *h_desc = F->h_blk + F->oD;
+    *h_kps_un = (const orbhip_keypoint *)(F->h_blk.as<uint8_t>() + F->oU);
+    *h_desc = F->h_blk.as<uint8_t>() + F->oD;
     return ORBHIP_OK;
 }
 

@@ -111,7 +111,7 @@ extern "C" int orbhip_search_by_projection_device(orbhip_ctx *c, const void *d_k
                                 cap, B, (const float *)d_u_right, (const uint8_t *)d_occupied, min_x, min_y, inv_w, inv_h,
                                 (const int32_t *)d_cell_off, (const int32_t *)d_cell_idx, (const orbhip_proj_query *)d_queries,
                                 (const uint8_t *)d_qdesc, (const int32_t *)d_nq, cap_q, use_ratio, nnratio, check_ori, th_high,
-                                (int32_t *)d_match, (int32_t *)d_nmatches, c->d_match);
+                                (int32_t *)d_match, (int32_t *)d_nmatches, c->d_match.as<void>());
     HIPCHK(c, hipGetLastError());
     return ORBHIP_OK;
 }
@@ -172,7 +172,7 @@ extern "C" int orbhip_window_best_device(orbhip_ctx *c, const void *d_kps, const
     launch_window_best(c->stream, (const orbhip_keypoint *)d_kps, (const uint8_t *)d_desc, cap, B, (const float *)d_u_right,
                        inv_level_sigma2, nlevels, min_x, min_y, inv_w, inv_h, (const int32_t *)d_cell_off,
                        (const int32_t *)d_cell_idx, (const orbhip_proj_query *)d_queries, (const uint8_t *)d_qdesc,
-                       (const int32_t *)d_nq, cap_q, (int32_t *)d_best_idx, (int32_t *)d_best_dist, c->d_match);
+                       (const int32_t *)d_nq, cap_q, (int32_t *)d_best_idx, (int32_t *)d_best_dist, c->d_match.as<void>());
     HIPCHK(c, hipGetLastError());
     return ORBHIP_OK;
 }
@@ -244,7 +244,7 @@ extern "C" int orbhip_search_for_initialization_device(orbhip_ctx *c, const void
                                      (const int32_t *)d_counts1, cap1, (const orbhip_keypoint *)d_kps2, (const uint8_t *)d_desc2,
                                      (const int32_t *)d_counts2, cap2, B, min_x, min_y, inv_w, inv_h, (const int32_t *)d_cell_off2,
                                      (const int32_t *)d_cell_idx2, (float *)d_prev_matched, window_size, nnratio, check_ori,
-                                     /*TH_LOW*/ 50, (int32_t *)d_matches12, (int32_t *)d_nmatches, c->d_match);
+                                     /*TH_LOW*/ 50, (int32_t *)d_matches12, (int32_t *)d_nmatches, c->d_match.as<void>());
     HIPCHK(c, hipGetLastError());
     return ORBHIP_OK;
 }

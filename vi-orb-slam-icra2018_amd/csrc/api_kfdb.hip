@@ -24,81 +24,40 @@ struct Kfdb {
     long long rebuilds = 0;
     bool mapDirty = true, deltaDirty = true;
     int nmap = 0;
-    size_t poolUsed = 0, poolCap = 0, pool2Cap = 0, sortCap = 0;
-    // device: database
-    uint32_t *d_row = nullptr, *d_tomb = nullptr, *d_poolW = nullptr, *d_pool2W = nullptr, *d_post = nullptr;
-    double *d_poolV = nullptr, *d_pool2V = nullptr;
-    uint4 *d_meta = nullptr;
-    uint64_t *d_nbKey = nullptr, *d_mapKey = nullptr, *d_slotKey = nullptr;
-    uint8_t *d_nbN = nullptr;
-    uint32_t *d_mapSlot = nullptr;
-    float *d_lastReloc = nullptr;
-    int32_t *d_delta = nullptr;
+    size_t poolUsed = 0;                 // entries of the pool in use (its capacity is d_poolW's)
+    // device: database (element types in the comments)
+    OrbBlock d_row, d_tomb, d_poolW, d_pool2W, d_post;   // uint32_t
+    OrbBlock d_poolV, d_pool2V;                          // double
+    OrbBlock d_meta;                                     // uint4
+    OrbBlock d_nbKey, d_mapKey, d_slotKey;               // uint64_t
+    OrbBlock d_nbN;                                      // uint8_t
+    OrbBlock d_mapSlot;                                  // uint32_t
+    OrbBlock d_lastReloc;                                // float
+    OrbBlock d_delta;                                    // int32_t
     // device: rebuild scratch
-    uint32_t *d_keys[2] = {nullptr, nullptr}, *d_vals[2] = {nullptr, nullptr};
-    int32_t *d_th = nullptr, *d_scan = nullptr;
-    size_t thCap = 0, scanCap = 0;
-    int4 *d_items = nullptr;
+    OrbBlock d_keys[2], d_vals[2];                       // uint32_t
+    OrbBlock d_th, d_scan;                               // int32_t
+    OrbBlock d_items;                                    // int4
     // device: per-batch state for up to capB queries
     int capB = 0;
-    int32_t *d_cnt = nullptr, *d_firstPos = nullptr, *d_touched = nullptr, *d_ordered = nullptr, *d_accBest = nullptr,
-            *d_cand = nullptr, *d_cntFirst = nullptr, *d_csrFirst = nullptr, *d_small = nullptr;
-    uint32_t *d_rank = nullptr;
-    float *d_score = nullptr, *d_accScore = nullptr;
-    uint8_t *d_excl = nullptr;
+    OrbBlock d_cnt, d_firstPos, d_touched, d_ordered, d_accBest, d_cand, d_cntFirst, d_csrFirst, d_small;   // int32_t
+    OrbBlock d_rank;                                     // uint32_t
+    OrbBlock d_score, d_accScore;                        // float
+    OrbBlock d_excl;                                     // uint8_t
     // orbhip_kfdb_set_timing: events at the phase boundaries of every query call, the last call's phase times
     hipEvent_t ev[KFDB_PHASES + 1] = {};
     bool timing = false;
     float phaseMs[KFDB_PHASES] = {};
 };
 
-static void dfree(void *&p)
+void orb_kfdb_release(orbhip_ctx *c)
 {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-template <class T>
-static void dfree(T *&p)
-{
-    void *v = p;
-    dfree(v);
-    p = nullptr;
-}
-
-static void batch_free(Kfdb *K)
-{
-    dfree(K->d_cnt), dfree(K->d_firstPos), dfree(K->d_touched), dfree(K->d_ordered), dfree(K->d_accBest), dfree(K->d_cand);
-    dfree(K->d_cntFirst), dfree(K->d_csrFirst), dfree(K->d_small), dfree(K->d_rank), dfree(K->d_score), dfree(K->d_accScore);
-    dfree(K->d_excl);
-    K->capB = 0;
-}
-
-static void kfdb_free(Kfdb *K)
-{
-    batch_free(K);
-    dfree(K->d_row), dfree(K->d_tomb), dfree(K->d_poolW), dfree(K->d_pool2W), dfree(K->d_post), dfree(K->d_poolV);
-    dfree(K->d_pool2V), dfree(K->d_meta), dfree(K->d_nbKey), dfree(K->d_mapKey), dfree(K->d_slotKey), dfree(K->d_nbN);
-    dfree(K->d_mapSlot), dfree(K->d_lastReloc), dfree(K->d_delta), dfree(K->d_keys[0]), dfree(K->d_keys[1]);
-    dfree(K->d_vals[0]), dfree(K->d_vals[1]), dfree(K->d_th), dfree(K->d_scan), dfree(K->d_items);
+    Kfdb *K = static_cast<Kfdb *>(c->kfdb);
+    if (!K) return;
     for (hipEvent_t &e : K->ev)
         if (e) (void)hipEventDestroy(e);
     delete K;
-}
-
-void orb_kfdb_release(orbhip_ctx *c)
-{
-    if (!c->kfdb) return;
-    kfdb_free(static_cast<Kfdb *>(c->kfdb));
     c->kfdb = nullptr;
-}
-
-template <class T>
-static int dalloc(orbhip_ctx *c, T *&p, size_t count)
-{
-    void *v = nullptr;
-    HIPCHK(c, hipMalloc(&v, count ? count * sizeof(T) : 16));
-    p = static_cast<T *>(v);
-    return ORBHIP_OK;
 }
 
 #define KCHK(expr)                    \
@@ -140,21 +99,21 @@ extern "C" int orbhip_kfdb_init(orbhip_ctx *c, int nwords, int max_kfs, int delt
     K->tomb.assign((max_kfs + 31) / 32, 0u);
     reset_slots(K);
     const size_t M = (size_t)max_kfs;
-    KCHK(dalloc(c, K->d_row, (size_t)nwords + 1));
-    KCHK(dalloc(c, K->d_tomb, K->tomb.size()));
-    KCHK(dalloc(c, K->d_meta, M));
-    KCHK(dalloc(c, K->d_nbKey, M * KFDB_MAX_NEIGH));
-    KCHK(dalloc(c, K->d_nbN, M));
-    KCHK(dalloc(c, K->d_mapKey, M));
-    KCHK(dalloc(c, K->d_mapSlot, M));
-    KCHK(dalloc(c, K->d_slotKey, M));
-    KCHK(dalloc(c, K->d_lastReloc, M));
-    KCHK(dalloc(c, K->d_delta, (size_t)K->deltaMax));
-    KCHK(dalloc(c, K->d_post, 1));
-    HIPCHK(c, hipMemsetAsync(K->d_row, 0, ((size_t)nwords + 1) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_tomb, 0, K->tomb.size() * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_nbN, 0, M, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_lastReloc, 0, M * 4, c->stream));
+    HIPCHK(c, K->d_row.grow(((size_t)nwords + 1) * 4));
+    HIPCHK(c, K->d_tomb.grow(K->tomb.size() * 4));
+    HIPCHK(c, K->d_meta.grow(M * sizeof(uint4)));
+    HIPCHK(c, K->d_nbKey.grow(M * KFDB_MAX_NEIGH * 8));
+    HIPCHK(c, K->d_nbN.grow(M));
+    HIPCHK(c, K->d_mapKey.grow(M * 8));
+    HIPCHK(c, K->d_mapSlot.grow(M * 4));
+    HIPCHK(c, K->d_slotKey.grow(M * 8));
+    HIPCHK(c, K->d_lastReloc.grow(M * 4));
+    HIPCHK(c, K->d_delta.grow((size_t)K->deltaMax * 4));
+    HIPCHK(c, K->d_post.grow(4));
+    HIPCHK(c, hipMemsetAsync(K->d_row.as<uint32_t>(), 0, ((size_t)nwords + 1) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_tomb.as<uint32_t>(), 0, K->tomb.size() * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_nbN.as<uint8_t>(), 0, M, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_lastReloc.as<float>(), 0, M * 4, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ORBHIP_OK;
 }
@@ -162,39 +121,24 @@ extern "C" int orbhip_kfdb_init(orbhip_ctx *c, int nwords, int max_kfs, int delt
 // the pool holds at least `need` entries (appends between rebuilds; a rebuild compacts it)
 static int pool_reserve(orbhip_ctx *c, Kfdb *K, size_t need)
 {
-    if (need <= K->poolCap) return ORBHIP_OK;
-    const size_t cap = std::max(need, std::max((size_t)1 << 16, K->poolCap * 2));
-    uint32_t *w = nullptr;
-    double *v = nullptr;
-    KCHK(dalloc(c, w, cap));
-    if (dalloc(c, v, cap)) {
-        dfree(w);
-        return ORBHIP_E_HIP;
-    }
+    const size_t poolCap = K->d_poolW.bytes() / 4;
+    if (need <= poolCap) return ORBHIP_OK;
+    const size_t cap = std::max(need, std::max((size_t)1 << 16, poolCap * 2));
+    OrbBlock w, v;
+    HIPCHK(c, w.grow(cap * 4));
+    HIPCHK(c, v.grow(cap * 8));
     if (K->poolUsed) {
-        HIPCHK(c, hipMemcpyAsync(w, K->d_poolW, K->poolUsed * 4, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(v, K->d_poolV, K->poolUsed * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(w.as<void>(), K->d_poolW.as<void>(), K->poolUsed * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(v.as<void>(), K->d_poolV.as<void>(), K->poolUsed * 8, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    dfree(K->d_poolW);
-    dfree(K->d_poolV);
-    K->d_poolW = w;
-    K->d_poolV = v;
-    K->poolCap = cap;
+    K->d_poolW = std::move(w);
+    K->d_poolV = std::move(v);
     return ORBHIP_OK;
 }
 
-template <class T>
-static int grow(orbhip_ctx *c, T *&p, size_t &cap, size_t need)
-{
-    if (need <= cap && p) return ORBHIP_OK;
-    dfree(p);
-    cap = 0;
-    const size_t n = std::max(need + need / 4, (size_t)4096);
-    KCHK(dalloc(c, p, n));
-    cap = n;
-    return ORBHIP_OK;
-}
+// entries of slack: what a rebuild buffer of `n` entries is allocated with
+static size_t slack(size_t n, size_t floor) { return std::max(n + n / 4, floor); }
 
 // Rebuild: the live key frames (CSR ones not erased, then the delta region -- add order) are copied to a compacted pool, their
 // (word, slot) pairs sorted by word (stable), the CSR rows recomputed.  Erased slots become free.
@@ -218,49 +162,42 @@ static int fold(orbhip_ctx *c, Kfdb *K)
         total += K->meta[s].y;
     }
     if (total > (size_t)INT32_MAX - (1 << 20)) return fail(c, ORBHIP_E_CAPACITY, "orbhip_kfdb: inverted file beyond 2^31 entries");
-    size_t cap = K->pool2Cap;
-    if (total > cap || !K->d_pool2W) {
-        dfree(K->d_pool2W);
-        dfree(K->d_pool2V);
-        cap = std::max(total + total / 4, (size_t)1 << 16);
-        KCHK(dalloc(c, K->d_pool2W, cap));
-        KCHK(dalloc(c, K->d_pool2V, cap));
-        K->pool2Cap = cap;
+    const size_t cap = slack(total, (size_t)1 << 16);   // entries of the compacted pool and the sort buffers when they grow
+    HIPCHK(c, K->d_pool2W.grow(total * 4, cap * 4));
+    HIPCHK(c, K->d_pool2V.grow(total * 8, cap * 8));
+    for (int b = 0; b < 2; b++) {
+        HIPCHK(c, K->d_keys[b].grow(total * 4, cap * 4));
+        HIPCHK(c, K->d_vals[b].grow(total * 4, cap * 4));
     }
-    if (total > K->sortCap || !K->d_keys[0]) {
-        for (int b = 0; b < 2; b++) dfree(K->d_keys[b]), dfree(K->d_vals[b]);
-        K->sortCap = std::max(total + total / 4, (size_t)1 << 16);
-        for (int b = 0; b < 2; b++) {
-            KCHK(dalloc(c, K->d_keys[b], K->sortCap));
-            KCHK(dalloc(c, K->d_vals[b], K->sortCap));
-        }
-    }
-    const size_t ntiles = (total + 4095) / 4096;
-    KCHK(grow(c, K->d_th, K->thCap, 256 * ntiles + 1));
-    KCHK(grow(c, K->d_scan, K->scanCap, (256 * ntiles + 2047) / 2048 + 1));
-    dfree(K->d_items);
-    KCHK(dalloc(c, K->d_items, items.size()));
+    const size_t ntiles = (total + 4095) / 4096, nth = 256 * ntiles + 1, nscan = (256 * ntiles + 2047) / 2048 + 1;
+    HIPCHK(c, K->d_th.grow(nth * 4, slack(nth, 4096) * 4));
+    HIPCHK(c, K->d_scan.grow(nscan * 4, slack(nscan, 4096) * 4));
+    K->d_items.reset();
+    HIPCHK(c, K->d_items.grow(items.size() * sizeof(int4)));
     if (!items.empty())
-        HIPCHK(c, hipMemcpyAsync(K->d_items, items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice, c->stream));
-    kfdb_fold_expand(c->stream, K->d_items, (int)items.size(), K->d_poolW, K->d_poolV, K->d_pool2W, K->d_pool2V, K->d_keys[0],
-                     K->d_vals[0]);
-    const int which = kfdb_radix_sort(c->stream, K->d_keys[0], K->d_vals[0], K->d_keys[1], K->d_vals[1], (int)total, K->nwords,
-                                      K->d_th, K->d_scan);
-    kfdb_rows(c->stream, K->d_keys[which], (int)total, K->nwords, K->d_row);
+        HIPCHK(c, hipMemcpyAsync(K->d_items.as<int4>(), items.data(), items.size() * sizeof(int4), hipMemcpyHostToDevice,
+                                 c->stream));
+    kfdb_fold_expand(c->stream, K->d_items.as<int4>(), (int)items.size(), K->d_poolW.as<uint32_t>(), K->d_poolV.as<double>(),
+                     K->d_pool2W.as<uint32_t>(), K->d_pool2V.as<double>(), K->d_keys[0].as<uint32_t>(),
+                     K->d_vals[0].as<uint32_t>());
+    const int which = kfdb_radix_sort(c->stream, K->d_keys[0].as<uint32_t>(), K->d_vals[0].as<uint32_t>(),
+                                      K->d_keys[1].as<uint32_t>(), K->d_vals[1].as<uint32_t>(), (int)total, K->nwords,
+                                      K->d_th.as<int32_t>(), K->d_scan.as<int32_t>());
+    kfdb_rows(c->stream, K->d_keys[which].as<uint32_t>(), (int)total, K->nwords, K->d_row.as<uint32_t>());
     HIPCHK(c, hipGetLastError());
     // the sorted slots are the postings; the other value buffer is scratch for the next rebuild
     std::swap(K->d_post, K->d_vals[which]);
     std::swap(K->d_poolW, K->d_pool2W);
     std::swap(K->d_poolV, K->d_pool2V);
-    std::swap(K->poolCap, K->pool2Cap);
     K->poolUsed = total;
     std::fill(K->tomb.begin(), K->tomb.end(), 0u);
-    HIPCHK(c, hipMemsetAsync(K->d_tomb, 0, K->tomb.size() * 4, c->stream));
-    HIPCHK(c, hipMemcpyAsync(K->d_meta, K->meta.data(), K->meta.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_tomb.as<uint32_t>(), 0, K->tomb.size() * 4, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_meta.as<uint4>(), K->meta.data(), K->meta.size() * sizeof(uint4), hipMemcpyHostToDevice,
+                             c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    // d_post's old buffer went to d_vals[which] (of any size): a fresh scratch buffer of sortCap entries takes its place
-    dfree(K->d_vals[which]);
-    KCHK(dalloc(c, K->d_vals[which], K->sortCap));
+    // d_post's old buffer went to d_vals[which] (of any size): a fresh scratch buffer as large as the others takes its place
+    K->d_vals[which].reset();
+    HIPCHK(c, K->d_vals[which].grow(K->d_keys[which].bytes()));
     K->csr = live;
     K->delta.clear();
     K->ntomb = 0;
@@ -297,13 +234,13 @@ extern "C" int orbhip_kfdb_add(orbhip_ctx *c, uint64_t key, const uint32_t *word
     const float zero = 0.f;
     const uint8_t none = 0;
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(K->d_poolW + K->poolUsed, word, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(K->d_poolV + K->poolUsed, value, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(K->d_poolW.as<uint32_t>() + K->poolUsed, word, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(K->d_poolV.as<double>() + K->poolUsed, value, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(c, hipMemcpyAsync(K->d_meta + s, &K->meta[s], sizeof(uint4), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(K->d_slotKey + s, &key, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(K->d_lastReloc + s, &zero, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(K->d_nbN + s, &none, 1, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_meta.as<uint4>() + s, &K->meta[s], sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_slotKey.as<uint64_t>() + s, &key, 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_lastReloc.as<float>() + s, &zero, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_nbN.as<uint8_t>() + s, &none, 1, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     K->poolUsed += (size_t)n;
     K->slotOf[key] = s;
@@ -332,7 +269,7 @@ extern "C" int orbhip_kfdb_erase(orbhip_ctx *c, uint64_t key)
     }
     K->tomb[s >> 5] |= 1u << (s & 31);
     K->ntomb++;
-    HIPCHK(c, hipMemcpyAsync(K->d_tomb + (s >> 5), &K->tomb[s >> 5], 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_tomb.as<uint32_t>() + (s >> 5), &K->tomb[s >> 5], 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (K->ntomb > std::max(256, (int)K->slotOf.size() / 4)) KCHK(fold(c, K));
     return ORBHIP_OK;
@@ -344,8 +281,8 @@ extern "C" int orbhip_kfdb_clear(orbhip_ctx *c)
     if (!K) return c ? fail(c, ORBHIP_E_ARG, "orbhip_kfdb_clear: no database (orbhip_kfdb_init)") : ORBHIP_E_ARG;
     HIPCHK(c, orb_enter(c));
     reset_slots(K);
-    HIPCHK(c, hipMemsetAsync(K->d_row, 0, ((size_t)K->nwords + 1) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_tomb, 0, K->tomb.size() * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_row.as<uint32_t>(), 0, ((size_t)K->nwords + 1) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_tomb.as<uint32_t>(), 0, K->tomb.size() * 4, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ORBHIP_OK;
 }
@@ -362,8 +299,9 @@ extern "C" int orbhip_kfdb_set_covis(orbhip_ctx *c, uint64_t key, const uint64_t
     const int s = it->second;
     const uint8_t nn = (uint8_t)n;
     if (n)
-        HIPCHK(c, hipMemcpyAsync(K->d_nbKey + (size_t)s * KFDB_MAX_NEIGH, neigh, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(K->d_nbN + s, &nn, 1, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(K->d_nbKey.as<uint64_t>() + (size_t)s * KFDB_MAX_NEIGH, neigh, (size_t)n * 8,
+                                 hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(K->d_nbN.as<uint8_t>() + s, &nn, 1, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return ORBHIP_OK;
 }
@@ -383,25 +321,19 @@ extern "C" int orbhip_kfdb_info(orbhip_ctx *c, int *live, int *delta, int *tombs
 static int batch_reserve(orbhip_ctx *c, Kfdb *K, int B)
 {
     if (B <= K->capB) return ORBHIP_OK;
-    batch_free(K);
+    K->capB = 0;
     const size_t BM = (size_t)B * K->maxKfs, BQ = (size_t)B * KFDB_MAX_QWORDS;
-    KCHK(dalloc(c, K->d_cnt, BM));
-    KCHK(dalloc(c, K->d_rank, BM));
-    KCHK(dalloc(c, K->d_score, BM));
-    KCHK(dalloc(c, K->d_excl, BM));
-    KCHK(dalloc(c, K->d_firstPos, BM));
-    KCHK(dalloc(c, K->d_touched, BM));
-    KCHK(dalloc(c, K->d_ordered, BM));
-    KCHK(dalloc(c, K->d_accScore, BM));
-    KCHK(dalloc(c, K->d_accBest, BM));
-    KCHK(dalloc(c, K->d_cand, BM));
-    KCHK(dalloc(c, K->d_cntFirst, BQ));
-    KCHK(dalloc(c, K->d_csrFirst, BQ));
-    KCHK(dalloc(c, K->d_small, (size_t)B * 5 + 8));
-    HIPCHK(c, hipMemsetAsync(K->d_cnt, 0, BM * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_rank, 0xFF, BM * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_excl, 0, BM, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_firstPos, 0x7F, BM * 4, c->stream));
+    for (OrbBlock *b : {&K->d_cnt, &K->d_rank, &K->d_score, &K->d_firstPos, &K->d_touched, &K->d_ordered, &K->d_accScore,
+                        &K->d_accBest, &K->d_cand})
+        HIPCHK(c, b->grow(BM * 4));
+    HIPCHK(c, K->d_excl.grow(BM));
+    HIPCHK(c, K->d_cntFirst.grow(BQ * 4));
+    HIPCHK(c, K->d_csrFirst.grow(BQ * 4));
+    HIPCHK(c, K->d_small.grow(((size_t)B * 5 + 8) * 4));
+    HIPCHK(c, hipMemsetAsync(K->d_cnt.as<int32_t>(), 0, BM * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_rank.as<uint32_t>(), 0xFF, BM * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_excl.as<uint8_t>(), 0, BM, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_firstPos.as<int32_t>(), 0x7F, BM * 4, c->stream));
     K->capB = B;
     return ORBHIP_OK;
 }
@@ -416,8 +348,9 @@ static int prepare(orbhip_ctx *c, Kfdb *K, int B, KfdbView &V)
         std::vector<uint32_t> slots(m.size());
         for (size_t i = 0; i < m.size(); i++) keys[i] = m[i].first, slots[i] = (uint32_t)m[i].second;
         if (!m.empty()) {
-            HIPCHK(c, hipMemcpyAsync(K->d_mapKey, keys.data(), keys.size() * 8, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(K->d_mapSlot, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(K->d_mapKey.as<uint64_t>(), keys.data(), keys.size() * 8, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(K->d_mapSlot.as<uint32_t>(), slots.data(), slots.size() * 4, hipMemcpyHostToDevice,
+                                     c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
         K->nmap = (int)m.size();
@@ -425,47 +358,48 @@ static int prepare(orbhip_ctx *c, Kfdb *K, int B, KfdbView &V)
     }
     if (K->deltaDirty) {
         if (!K->delta.empty())
-            HIPCHK(c, hipMemcpyAsync(K->d_delta, K->delta.data(), K->delta.size() * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(K->d_delta.as<int32_t>(), K->delta.data(), K->delta.size() * 4, hipMemcpyHostToDevice,
+                                     c->stream));
         K->deltaDirty = false;
     }
     KCHK(batch_reserve(c, K, B));
     V.nwords = K->nwords;
     V.maxKfs = K->maxKfs;
-    V.row = K->d_row;
-    V.post = K->d_post;
-    V.tomb = K->d_tomb;
-    V.meta = K->d_meta;
-    V.poolW = K->d_poolW;
-    V.poolV = K->d_poolV;
-    V.delta = K->d_delta;
+    V.row = K->d_row.as<uint32_t>();
+    V.post = K->d_post.as<uint32_t>();
+    V.tomb = K->d_tomb.as<uint32_t>();
+    V.meta = K->d_meta.as<uint4>();
+    V.poolW = K->d_poolW.as<uint32_t>();
+    V.poolV = K->d_poolV.as<double>();
+    V.delta = K->d_delta.as<int32_t>();
     V.ndelta = (int)K->delta.size();
-    V.nbKey = K->d_nbKey;
-    V.nbN = K->d_nbN;
-    V.mapKey = K->d_mapKey;
-    V.mapSlot = K->d_mapSlot;
+    V.nbKey = K->d_nbKey.as<uint64_t>();
+    V.nbN = K->d_nbN.as<uint8_t>();
+    V.mapKey = K->d_mapKey.as<uint64_t>();
+    V.mapSlot = K->d_mapSlot.as<uint32_t>();
     V.nmap = K->nmap;
-    V.slotKey = K->d_slotKey;
-    V.lastReloc = K->d_lastReloc;
+    V.slotKey = K->d_slotKey.as<uint64_t>();
+    V.lastReloc = K->d_lastReloc.as<float>();
     V.B = B;
-    V.cnt = K->d_cnt;
-    V.rank = K->d_rank;
-    V.score = K->d_score;
-    V.excl = K->d_excl;
-    V.firstPos = K->d_firstPos;
-    V.touched = K->d_touched;
-    V.ordered = K->d_ordered;
-    V.accScore = K->d_accScore;
-    V.accBest = K->d_accBest;
-    V.cand = K->d_cand;
-    V.cntFirst = K->d_cntFirst;
-    V.csrFirst = K->d_csrFirst;
-    V.tcount = K->d_small;
-    V.maxc = K->d_small + B;
-    V.minc = K->d_small + 2 * B;
-    V.outCnt = K->d_small + 3 * B;
-    V.status = K->d_small + 4 * B;
-    HIPCHK(c, hipMemsetAsync(K->d_small, 0, ((size_t)B * 5 + 8) * 4, c->stream));
-    HIPCHK(c, hipMemsetAsync(K->d_cntFirst, 0, (size_t)B * KFDB_MAX_QWORDS * 4, c->stream));
+    V.cnt = K->d_cnt.as<int32_t>();
+    V.rank = K->d_rank.as<uint32_t>();
+    V.score = K->d_score.as<float>();
+    V.excl = K->d_excl.as<uint8_t>();
+    V.firstPos = K->d_firstPos.as<int32_t>();
+    V.touched = K->d_touched.as<int32_t>();
+    V.ordered = K->d_ordered.as<int32_t>();
+    V.accScore = K->d_accScore.as<float>();
+    V.accBest = K->d_accBest.as<int32_t>();
+    V.cand = K->d_cand.as<int32_t>();
+    V.cntFirst = K->d_cntFirst.as<int32_t>();
+    V.csrFirst = K->d_csrFirst.as<int32_t>();
+    V.tcount = K->d_small.as<int32_t>();
+    V.maxc = K->d_small.as<int32_t>() + B;
+    V.minc = K->d_small.as<int32_t>() + 2 * B;
+    V.outCnt = K->d_small.as<int32_t>() + 3 * B;
+    V.status = K->d_small.as<int32_t>() + 4 * B;
+    HIPCHK(c, hipMemsetAsync(K->d_small.as<int32_t>(), 0, ((size_t)B * 5 + 8) * 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(K->d_cntFirst.as<int32_t>(), 0, (size_t)B * KFDB_MAX_QWORDS * 4, c->stream));
     return ORBHIP_OK;
 }
 
@@ -656,7 +590,7 @@ extern "C" int orbhip_kfdb_detect_device(orbhip_ctx *c, int mode, int B, const v
         return fail(c, ORBHIP_E_ARG, "orbhip_kfdb_detect_device: null pointer");
     HIPCHK(c, orb_enter(c));
     if (orb_host_stage(c, 64)) return ORBHIP_E_HIP;
-    int32_t *h = (int32_t *)c->h_stage;   // qoff[0] | qoff[B] | xoff[0] | xoff[B] | status | out_off[B]
+    int32_t *h = (int32_t *)c->h_stage.as<uint8_t>();   // qoff[0] | qoff[B] | xoff[0] | xoff[B] | status | out_off[B]
     HIPCHK(c, hipMemcpyAsync(h + 0, d_qoff, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h + 1, (const int32_t *)d_qoff + B, 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(h + 2, d_xoff, 4, hipMemcpyDeviceToHost, c->stream));

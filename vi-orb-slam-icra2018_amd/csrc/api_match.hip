@@ -8,12 +8,7 @@
 // ------------------------------------------------------------------------------------------------
 int orb_match_scratch(orbhip_ctx *c, size_t bytes)
 {
-    if (bytes <= c->d_match_bytes && c->d_match) return ORBHIP_OK;
-    if (c->d_match) HIPCHK(c, hipFree(c->d_match));
-    c->d_match = nullptr;
-    c->d_match_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_match, bytes));
-    c->d_match_bytes = bytes;
+    HIPCHK(c, c->d_match.grow(bytes));
     return ORBHIP_OK;
 }
 
@@ -29,7 +24,7 @@ extern "C" int orbhip_hamming_knn2_device(orbhip_ctx *c, const void *d_q, int nq
     if ((rc = orb_match_scratch(c, need))) return rc;
     if (c->stageTiming >= 2) HIPCHK(c, hipEventRecord(c->ev[6], c->stream));
     launch_knn2(c->stream, (const uint8_t *)d_q, nq, (const uint8_t *)d_db, ndb, (int32_t *)d_best_idx,
-                (int32_t *)d_best_d, (int32_t *)d_second_d, c->d_match, need);
+                (int32_t *)d_best_d, (int32_t *)d_second_d, c->d_match.as<void>(), need);
     if (c->stageTiming >= 2) HIPCHK(c, hipEventRecord(c->ev[7], c->stream));
     HIPCHK(c, hipGetLastError());
     c->haveMatchEvents = c->stageTiming >= 2;
@@ -282,10 +277,9 @@ extern "C" int orbhip_vocab_load(orbhip_ctx *c, const void *blob, size_t nbytes)
     // The new tables are complete before the context sees them; the swap happens under vocMutex, so that a borrower's
     // orbhip_vocab_share / orbhip_vocab_generation on another thread reads either the old pair or the new one.
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    void *blk = nullptr;
-    HIPCHK(c, hipMalloc(&blk, total));
-    std::shared_ptr<void> hold(blk, [](void *p) { (void)hipFree(p); });
-    uint8_t *base = (uint8_t *)blk;
+    auto hold = std::make_shared<OrbBlock>();
+    HIPCHK(c, hold->grow(total));
+    uint8_t *base = hold->as<uint8_t>();
     const void *src[5] = {H.edesc.data(), H.erange.data(), H.child.data(), H.eword.data(), H.eweight.data()};
     for (int i = 0; i < 5; i++) HIPCHK(c, hipMemcpyAsync(base + off[i], src[i], sizes[i], hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -325,7 +319,7 @@ extern "C" int orbhip_vocab_share(orbhip_ctx *dst, const orbhip_ctx *src)
 {
     if (!dst || !src) return fail(dst, ORBHIP_E_ARG, "orbhip_vocab_share: no vocabulary in the source context");
     if (dst == src) return src->voc.desc ? ORBHIP_OK : fail(dst, ORBHIP_E_ARG, "orbhip_vocab_share: no vocabulary in the source context");
-    std::shared_ptr<void> hold;
+    std::shared_ptr<OrbBlock> hold;
     OrbVocabDev V;
     {
         std::lock_guard<std::mutex> g(src->vocMutex);   // a consistent (block, tables) pair while the lender may be loading

@@ -11,13 +11,6 @@ void orb_pipe_release(orbhip_ctx *c)
     if (!P) return;
     if (P->sIn) (void)hipStreamSynchronize(P->sIn);
     if (P->sOut) (void)hipStreamSynchronize(P->sOut);
-    for (uint8_t *p : P->d_in)
-        if (p) (void)hipFree(p);
-    for (uint8_t *p : P->d_out)
-        if (p) (void)hipFree(p);
-    for (uint8_t *p : P->h_out)
-        if (p) (void)hipHostFree(p);
-    if (P->d_bowScratch) (void)hipFree(P->d_bowScratch);
     for (auto *v : {&P->evIn, &P->evK, &P->evOut})
         for (hipEvent_t e : *v)
             if (e) (void)hipEventDestroy(e);
@@ -73,23 +66,18 @@ extern "C" int orbhip_pipe_create(orbhip_ctx *c, int depth, int B, int w, int h)
     hipError_t e;
     if ((e = hipStreamCreateWithFlags(&P->sIn, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
     if ((e = hipStreamCreateWithFlags(&P->sOut, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", e);
-    P->d_in.assign(depth, nullptr); P->d_out.assign(depth, nullptr); P->h_out.assign(depth + 1, nullptr);
+    P->d_in.resize(depth); P->d_out.resize(depth);
+    for (int i = 0; i <= depth; i++) P->h_out.emplace_back(OrbBlock::Host);
     P->evIn.assign(depth, nullptr); P->evK.assign(depth, nullptr); P->evOut.assign(depth, nullptr);
     P->slotB.assign(depth, 0);
     for (int i = 0; i < depth; i++) {
-        void *p = nullptr;
-        if ((e = hipMalloc(&p, P->inBytes)) != hipSuccess) return bail("hipMalloc (input slot)", e);
-        P->d_in[i] = (uint8_t *)p;
-        if ((e = hipMalloc(&p, P->outBytes)) != hipSuccess) return bail("hipMalloc (output slot)", e);
-        P->d_out[i] = (uint8_t *)p;
+        if ((e = P->d_in[i].grow(P->inBytes)) != hipSuccess) return bail("hipMalloc (input slot)", e);
+        if ((e = P->d_out[i].grow(P->outBytes)) != hipSuccess) return bail("hipMalloc (output slot)", e);
         for (hipEvent_t *ev : {&P->evIn[i], &P->evK[i], &P->evOut[i]})
             if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", e);
     }
-    for (int i = 0; i <= depth; i++) {
-        void *p = nullptr;
-        if ((e = hipHostMalloc(&p, P->outBytes, hipHostMallocDefault)) != hipSuccess) return bail("hipHostMalloc (result block)", e);
-        P->h_out[i] = (uint8_t *)p;
-    }
+    for (OrbBlock &b : P->h_out)
+        if ((e = b.grow(P->outBytes)) != hipSuccess) return bail("hipHostMalloc (result block)", e);
     return ORBHIP_OK;
 }
 
@@ -120,20 +108,23 @@ extern "C" int orbhip_pipe_submit(orbhip_ctx *c, const uint8_t *frames, int B, i
     // copy in: the slot's previous kernels must have read it (evK of the batch `depth` submissions ago)
     if (P->submitted >= P->depth) HIPCHK(c, hipStreamWaitEvent(P->sIn, P->evK[s], 0));
     if (stride == P->stride && (size_t)stride * P->h == P->frameBytes && frame_stride == P->frameBytes) {
-        HIPCHK(c, hipMemcpyAsync(P->d_in[s], frames, P->frameBytes * B, hipMemcpyHostToDevice, P->sIn));      // one contiguous block
+        HIPCHK(c, hipMemcpyAsync(P->d_in[s].as<uint8_t>(), frames, P->frameBytes * B, hipMemcpyHostToDevice,
+                                 P->sIn));      // one contiguous block
     } else if (stride == P->stride) {
         // whole frames are contiguous on both sides: a 2-D copy with one "row" per frame
-        HIPCHK(c, hipMemcpy2DAsync(P->d_in[s], P->frameBytes, frames, frame_stride, (size_t)stride * (P->h - 1) + P->w, B,
+        HIPCHK(c, hipMemcpy2DAsync(P->d_in[s].as<uint8_t>(), P->frameBytes, frames, frame_stride,
+                                   (size_t)stride * (P->h - 1) + P->w, B,
                                    hipMemcpyHostToDevice, P->sIn));
     } else {
         hipMemcpy3DParms q = {};
         q.srcPtr = make_hipPitchedPtr(const_cast<uint8_t *>(frames), stride, P->w, frame_stride / stride);
-        q.dstPtr = make_hipPitchedPtr(P->d_in[s], P->stride, P->w, P->frameBytes / P->stride);
+        q.dstPtr = make_hipPitchedPtr(P->d_in[s].as<uint8_t>(), P->stride, P->w, P->frameBytes / P->stride);
         q.extent = make_hipExtent(P->w, P->h, B);
         q.kind = hipMemcpyHostToDevice;
         if (frame_stride % stride != 0 || P->frameBytes % P->stride != 0) {
             for (int b = 0; b < B; b++)   // pitches that are not whole rows: frame by frame
-                HIPCHK(c, hipMemcpy2DAsync(P->d_in[s] + (size_t)b * P->frameBytes, P->stride, frames + (size_t)b * frame_stride, stride,
+                HIPCHK(c, hipMemcpy2DAsync(P->d_in[s].as<uint8_t>() + (size_t)b * P->frameBytes, P->stride,
+                                           frames + (size_t)b * frame_stride, stride,
                                            P->w, P->h, hipMemcpyHostToDevice, P->sIn));
         } else {
             HIPCHK(c, hipMemcpy3DAsync(&q, P->sIn));
@@ -143,8 +134,9 @@ extern "C" int orbhip_pipe_submit(orbhip_ctx *c, const uint8_t *frames, int B, i
     // compute: after the copy, and after the previous results of this output slot have left the device
     HIPCHK(c, hipStreamWaitEvent(c->stream, P->evIn[s], 0));
     if (P->submitted >= P->depth) HIPCHK(c, hipStreamWaitEvent(c->stream, P->evOut[s], 0));
-    uint8_t *blk = P->d_out[s];
-    if ((rc = orb_run_pipeline(c, P->d_in[s], P->stride, P->frameBytes, B, (orbhip_keypoint *)(blk + P->koff), blk + P->doff,
+    uint8_t *blk = P->d_out[s].as<uint8_t>();
+    if ((rc = orb_run_pipeline(c, P->d_in[s].as<uint8_t>(), P->stride, P->frameBytes, B, (orbhip_keypoint *)(blk + P->koff),
+                               blk + P->doff,
                            (int32_t *)(blk + P->coff), P->dcap)))
         return rc;
     size_t outBytes = P->coff + (size_t)B * 4;
@@ -152,7 +144,7 @@ extern "C" int orbhip_pipe_submit(orbhip_ctx *c, const uint8_t *frames, int B, i
         // Frame::ComputeBoW (src/Frame.cc:739-746) + ORBmatcher::SearchByBoW of every frame against its predecessor in the batch
         // (Tracking::TrackReferenceKeyFrame, src/Tracking.cc:1881-1885), on the slot's device-resident outputs
         const size_t n = (size_t)B * P->dcap;
-        int32_t *word = (int32_t *)P->d_bowScratch, *node = word + 2 * (size_t)P->B * P->dcap;
+        int32_t *word = P->d_bowScratch.as<int32_t>(), *node = word + 2 * (size_t)P->B * P->dcap;
         float *wt = (float *)(word + (size_t)P->B * P->dcap);
         if ((rc = orbhip_vocab_transform_device(c, blk + P->doff, (int)n, P->levelsup, word, wt, node))) return rc;
         if ((rc = orbhip_search_by_bow_seq_device(c, blk + P->doff, blk + P->koff, blk + P->coff, node, wt, nullptr, P->dcap, B, 1, 0,
@@ -163,7 +155,7 @@ extern "C" int orbhip_pipe_submit(orbhip_ctx *c, const uint8_t *frames, int B, i
     HIPCHK(c, hipEventRecord(P->evK[s], c->stream));
     // copy out
     HIPCHK(c, hipStreamWaitEvent(P->sOut, P->evK[s], 0));
-    HIPCHK(c, hipMemcpyAsync(P->h_out[hb], blk, outBytes, hipMemcpyDeviceToHost, P->sOut));
+    HIPCHK(c, hipMemcpyAsync(P->h_out[hb].as<uint8_t>(), blk, outBytes, hipMemcpyDeviceToHost, P->sOut));
     HIPCHK(c, hipEventRecord(P->evOut[s], P->sOut));
     P->slotB[s] = B;
     P->submitted++;
@@ -179,9 +171,9 @@ extern "C" int orbhip_pipe_wait(orbhip_ctx *c, const orbhip_keypoint **kps, cons
     HIPCHK(c, orb_enter(c));
     const int s = (int)(P->waited % P->depth), hb = (int)(P->waited % (P->depth + 1));
     HIPCHK(c, hipEventSynchronize(P->evOut[s]));
-    if (kps) *kps = (const orbhip_keypoint *)(P->h_out[hb] + P->koff);
-    if (desc) *desc = P->h_out[hb] + P->doff;
-    if (n_out) *n_out = (const int32_t *)(P->h_out[hb] + P->coff);
+    if (kps) *kps = (const orbhip_keypoint *)(P->h_out[hb].as<uint8_t>() + P->koff);
+    if (desc) *desc = P->h_out[hb].as<uint8_t>() + P->doff;
+    if (n_out) *n_out = (const int32_t *)(P->h_out[hb].as<uint8_t>() + P->coff);
     if (B) *B = P->slotB[s];
     if (cap) *cap = P->dcap;
     P->lastWaited = hb;
@@ -196,11 +188,7 @@ extern "C" int orbhip_pipe_enable_bow(orbhip_ctx *c, int levelsup, float nnratio
     OrbPipe *P = c->pipe;
     if (P->dcap > 4096) return fail(c, ORBHIP_E_SIZE, "orbhip_pipe_enable_bow: more than 4096 feature slots per frame");
     HIPCHK(c, orb_enter(c));
-    if (!P->d_bowScratch) {
-        void *p = nullptr;
-        HIPCHK(c, hipMalloc(&p, (size_t)P->B * P->dcap * 12 + 256));
-        P->d_bowScratch = (uint8_t *)p;
-    }
+    if (!P->d_bowScratch) HIPCHK(c, P->d_bowScratch.grow((size_t)P->B * P->dcap * 12 + 256));
     P->bow = true;
     P->levelsup = levelsup;
     P->nnratio = nnratio;
@@ -213,7 +201,7 @@ extern "C" int orbhip_pipe_matches(orbhip_ctx *c, const int32_t **match12, const
     if (!c || !c->pipe || !c->pipe->bow || c->pipe->lastWaited < 0)
         return fail(c, ORBHIP_E_ARG, "orbhip_pipe_matches: no batch with matches has been collected");
     OrbPipe *P = c->pipe;
-    const uint8_t *h = P->h_out[P->lastWaited];
+    const uint8_t *h = P->h_out[P->lastWaited].as<uint8_t>();
     if (match12) *match12 = (const int32_t *)(h + P->m12off);
     if (match21) *match21 = (const int32_t *)(h + P->m21off);
     if (nmatches) *nmatches = (const int32_t *)(h + P->nmoff);

@@ -14,8 +14,8 @@
 // one device-to-device copy.  Blocks and their page-locked CSR staging are pooled: a frame per camera image enters and
 // leaves the table, and a hipMalloc / hipHostMalloc pair per frame would cost more than the search it serves.
 struct OrbSetMem {
-    uint8_t *block = nullptr;          // device
-    uint8_t *h_csr = nullptr;          // page-locked: CSR offsets | CSR indices on their way to the device
+    OrbBlock block;                    // device
+    OrbBlock h_csr{OrbBlock::Host};    // page-locked: CSR offsets | CSR indices on their way to the device
     int capN = 0;
     size_t bytes = 0, oK = 0, oD = 0, oC = 0, oG = 0, oE = 0, oO = 0, oI = 0, csrBytes = 0;
 };
@@ -47,13 +47,6 @@ static OrbSetTable *table(orbhip_ctx *c)
     return static_cast<OrbSetTable *>(c->setTable);
 }
 
-static void mem_free(OrbSetMem &m)
-{
-    if (m.block) (void)hipFree(m.block);
-    if (m.h_csr) (void)hipHostFree(m.h_csr);
-    m = OrbSetMem();
-}
-
 static void mem_layout(OrbSetMem &m, int capN)
 {
     size_t o = 0;
@@ -73,12 +66,7 @@ static void mem_layout(OrbSetMem &m, int capN)
 // a set leaves the table: its memory goes to the pool (the caller has made sure no queued kernel reads it)
 static void set_retire(OrbSetTable *T, OrbSet *s)
 {
-    if (s->mem.block) {
-        if (T->pool.size() < 8)
-            T->pool.push_back(s->mem);
-        else
-            mem_free(s->mem);
-    }
+    if (s->mem.block && T->pool.size() < 8) T->pool.push_back(std::move(s->mem));
     delete s;
 }
 
@@ -86,11 +74,7 @@ void orb_sets_release(orbhip_ctx *c)
 {
     if (!c->setTable) return;
     OrbSetTable *T = static_cast<OrbSetTable *>(c->setTable);
-    for (OrbSet *s : T->sets) {
-        mem_free(s->mem);
-        delete s;
-    }
-    for (OrbSetMem &m : T->pool) mem_free(m);
+    for (OrbSet *s : T->sets) delete s;
     delete T;
     c->setTable = nullptr;
 }
@@ -186,36 +170,32 @@ static OrbSet *set_acquire(orbhip_ctx *c, uint64_t key, int n, int capWant = 0)
                         : (T->pool[i].capN >= n && (best < 0 || T->pool[i].capN < T->pool[best].capN)))
             best = (int)i;
     if (best >= 0) {
-        s->mem = T->pool[best];
+        s->mem = std::move(T->pool[best]);
         T->pool.erase(T->pool.begin() + best);
     } else {
         // capacity in steps of 256 features, so that the frames of a sequence (whose counts differ by a few) share blocks
         mem_layout(s->mem, capWant > 0 ? capWant : (int)align_up((size_t)n + 8, 256));
-        void *p = nullptr;
-        if (hipMalloc(&p, s->mem.bytes) != hipSuccess) {
+        if (s->mem.block.grow(s->mem.bytes) != hipSuccess) {
             (void)hipGetLastError();
             delete s;
             return fail(c, ORBHIP_E_HIP, "orbhip_set_put: out of device memory"), nullptr;
         }
-        s->mem.block = (uint8_t *)p;
-        if (hipHostMalloc(&p, s->mem.csrBytes, hipHostMallocDefault) != hipSuccess) {
+        if (s->mem.h_csr.grow(s->mem.csrBytes) != hipSuccess) {
             (void)hipGetLastError();
-            mem_free(s->mem);
             delete s;
             return fail(c, ORBHIP_E_HIP, "orbhip_set_put: out of page-locked memory"), nullptr;
         }
-        s->mem.h_csr = (uint8_t *)p;
     }
     const OrbSetMem &m = s->mem;
     s->key = key;
     s->n = n;
-    s->d_kps = (orbhip_keypoint *)(m.block + m.oK);
-    s->d_desc = m.block + m.oD;
-    s->d_cnt = (int32_t *)(m.block + m.oC);
-    s->d_cellOff = (int32_t *)(m.block + m.oG);
-    s->d_cellIdx = (int32_t *)(m.block + m.oE);
-    s->d_off = (int32_t *)(m.block + m.oO);
-    s->d_idx = (int32_t *)(m.block + m.oI);
+    s->d_kps = (orbhip_keypoint *)(m.block.as<uint8_t>() + m.oK);
+    s->d_desc = m.block.as<uint8_t>() + m.oD;
+    s->d_cnt = (int32_t *)(m.block.as<uint8_t>() + m.oC);
+    s->d_cellOff = (int32_t *)(m.block.as<uint8_t>() + m.oG);
+    s->d_cellIdx = (int32_t *)(m.block.as<uint8_t>() + m.oE);
+    s->d_off = (int32_t *)(m.block.as<uint8_t>() + m.oO);
+    s->d_idx = (int32_t *)(m.block.as<uint8_t>() + m.oI);
     return s;
 }
 
@@ -242,12 +222,13 @@ static hipError_t csr_upload(orbhip_ctx *c, OrbSet *s, const int32_t *node, cons
         s->node.assign(node, node + ng);
         s->off.assign(off, off + ng + 1);
         s->idx.assign(idx, idx + cnt);
-        memcpy(m.h_csr, off, (size_t)(ng + 1) * 4);
-        memcpy(m.h_csr + (m.oI - m.oO), idx, (size_t)cnt * 4);
+        memcpy(m.h_csr.as<uint8_t>(), off, (size_t)(ng + 1) * 4);
+        memcpy(m.h_csr.as<uint8_t>() + (m.oI - m.oO), idx, (size_t)cnt * 4);
     } else {
-        memset(m.h_csr, 0, 4);
+        memset(m.h_csr.as<uint8_t>(), 0, 4);
     }
-    return hipMemcpyAsync(m.block + m.oO, m.h_csr, (m.oI - m.oO) + (size_t)cnt * 4 + 4, hipMemcpyHostToDevice, c->stream);
+    return hipMemcpyAsync(m.block.as<uint8_t>() + m.oO, m.h_csr.as<uint8_t>(), (m.oI - m.oO) + (size_t)cnt * 4 + 4,
+                          hipMemcpyHostToDevice, c->stream);
 }
 
 extern "C" int orbhip_set_put(orbhip_ctx *c, uint64_t key, const orbhip_keypoint *kps, const uint8_t *desc, int n,
@@ -276,7 +257,7 @@ extern "C" int orbhip_set_put(orbhip_ctx *c, uint64_t key, const orbhip_keypoint
     memcpy(P.h + m.oD, desc, (size_t)n * 32);
     const int32_t cnt[4] = {n, 0, 0, 0};
     memcpy(P.h + m.oC, cnt, 16);
-    hipError_t e = hipMemcpyAsync(m.block, P.h, m.oC + 16, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(m.block.as<uint8_t>(), P.h, m.oC + 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = csr_upload(c, s, node, off, idx, ng);
     if (e == hipSuccess && s->grid) {
         launch_grid_build(c->stream, s->d_kps, s->d_cnt, m.capN, 1, min_x, min_y, inv_w, inv_h, s->d_cellOff, s->d_cellIdx);
@@ -335,10 +316,12 @@ extern "C" int orbhip_set_put_from_frame(orbhip_ctx *c, uint64_t key, orbhip_ctx
     const size_t to[5] = {m.oK, m.oD, m.oC, m.oG, m.oE};
     hipError_t e = hipSuccess;
     if (m.capN == dcap) {
-        e = hipMemcpyAsync(m.block, blk, grid ? so[4] + part[4] : so[2] + 16, hipMemcpyDeviceToDevice, c->stream);   // identical layouts: one copy
+        e = hipMemcpyAsync(m.block.as<uint8_t>(), blk, grid ? so[4] + part[4] : so[2] + 16, hipMemcpyDeviceToDevice,
+                           c->stream);   // identical layouts: one copy
     } else {
         for (int k = 0; k < 5 && e == hipSuccess; k++)
-            if (part[k]) e = hipMemcpyAsync(m.block + to[k], blk + so[k], part[k], hipMemcpyDeviceToDevice, c->stream);
+            if (part[k]) e = hipMemcpyAsync(m.block.as<uint8_t>() + to[k], blk + so[k], part[k], hipMemcpyDeviceToDevice,
+                                            c->stream);
     }
     if (e == hipSuccess) e = csr_upload(c, s, node, off, idx, ng);
     if (e == hipSuccess && orb_frame_mark_busy(src, c->stream) != ORBHIP_OK) e = hipErrorUnknown;

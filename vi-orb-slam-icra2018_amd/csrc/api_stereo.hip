@@ -24,7 +24,7 @@ extern "C" int orbhip_stereo_match_device(orbhip_ctx *L, orbhip_ctx *R, const vo
     HIPCHK(L, hipStreamWaitEvent(L->stream, R->evx[0], 0));
     launch_stereo(L, R, (const orbhip_keypoint *)d_kpsL, (const uint8_t *)d_descL, (const int32_t *)d_cntL,
                   (const orbhip_keypoint *)d_kpsR, (const uint8_t *)d_descR, (const int32_t *)d_cntR, cap, B, mb, mbf,
-                  (float *)d_uRight, (float *)d_depth, (int32_t *)L->d_match, (int32_t *)d_nmatch);
+                  (float *)d_uRight, (float *)d_depth, L->d_match.as<int32_t>(), (int32_t *)d_nmatch);
     HIPCHK(L, hipGetLastError());
     // ... and the right context must not overwrite its pyramid before these kernels have read it
     HIPCHK(L, hipEventRecord(L->evx[0], L->stream));
@@ -121,13 +121,12 @@ extern "C" int orbhip_remap_set_maps(orbhip_ctx *c, const float *map_x, const fl
     if (!c || !map_x || !map_y || w <= 0 || h <= 0) return fail(c, ORBHIP_E_ARG, "orbhip_remap_set_maps: bad argument");
     HIPCHK(c, orb_enter(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_maps) HIPCHK(c, hipFree(c->d_maps));
-    c->d_maps = nullptr;
+    c->d_maps.reset();
     c->map_w = c->map_h = 0;
     const size_t n = (size_t)w * h;
-    HIPCHK(c, hipMalloc((void **)&c->d_maps, 2 * n * sizeof(float) + 64));
-    HIPCHK(c, hipMemcpy(c->d_maps, map_x, n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(c->d_maps + n, map_y, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, c->d_maps.grow(2 * n * sizeof(float) + 64));
+    HIPCHK(c, hipMemcpy(c->d_maps.as<float>(), map_x, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(c->d_maps.as<float>() + n, map_y, n * sizeof(float), hipMemcpyHostToDevice));
     c->map_w = w;
     c->map_h = h;
     return ORBHIP_OK;
@@ -141,8 +140,9 @@ extern "C" int orbhip_remap_device(orbhip_ctx *c, const void *d_src, int B, int 
     if (!c->d_maps) return fail(c, ORBHIP_E_ARG, "orbhip_remap_device: no maps (orbhip_remap_set_maps)");
     if (dst_stride < c->map_w) return fail(c, ORBHIP_E_ARG, "orbhip_remap_device: dst_stride smaller than the map width");
     HIPCHK(c, orb_enter(c));
-    launch_remap(c->stream, (const uint8_t *)d_src, B, src_w, src_h, src_stride, src_frame_stride, c->d_maps,
-                 c->d_maps + (size_t)c->map_w * c->map_h, c->map_w, c->map_h, (uint8_t *)d_dst, dst_stride, dst_frame_stride);
+    launch_remap(c->stream, (const uint8_t *)d_src, B, src_w, src_h, src_stride, src_frame_stride, c->d_maps.as<float>(),
+                 c->d_maps.as<float>() + (size_t)c->map_w * c->map_h, c->map_w, c->map_h, (uint8_t *)d_dst, dst_stride,
+                 dst_frame_stride);
     HIPCHK(c, hipGetLastError());
     return ORBHIP_OK;
 }

@@ -400,8 +400,9 @@ int launch_stereo(orbhip_ctx *L, orbhip_ctx *R, const orbhip_keypoint *kpsL, con
     hipLaunchKernelGGL(k_stereo_rows, dim3(B, 1, 1), dim3(256, 1, 1), 0, s, G, kpsR, cntR, cap, entCap, off, ent);
     hipLaunchKernelGGL(k_stereo_best, dim3((cap + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, G, kpsL, descL, cntL, kpsR, descR,
                        cntR, cap, entCap, off, ent, maxD, bestUR, bestDist);
-    hipLaunchKernelGGL(k_stereo_refine, dim3((cap + 3) / 4, B, 1), dim3(256, 1, 1), 0, s, G, L->last_lvl0, L->d_pyr, R->last_lvl0,
-                       R->d_pyr, kpsL, cntL, bestUR, bestDist, cap, maxD, mbf, uRight, depth, sad);
+    hipLaunchKernelGGL(k_stereo_refine, dim3((cap + 3) / 4, B, 1), dim3(256, 1, 1), 0, s, G, L->last_lvl0,
+                       L->d_pyr.as<uint8_t>(), R->last_lvl0,
+                       R->d_pyr.as<uint8_t>(), kpsL, cntL, bestUR, bestDist, cap, maxD, mbf, uRight, depth, sad);
     hipLaunchKernelGGL(k_stereo_cut, dim3(B, 1, 1), dim3(256, 1, 1), 0, s, cntL, cap, sad, uRight, depth, nmatch);
     return ORBHIP_OK;
 }

@@ -181,14 +181,82 @@ struct OrbVocabDev {
     unsigned long long gen = 0;               // process-wide load counter (orbhip_vocab_generation): which load these tables are
 };
 
+// One owned block of device memory (hipMalloc) or page-locked host memory (hipHostMalloc).  Every buffer of the library's host
+// code is one of these -- orbhip_host_alloc's blocks, which belong to the caller, excepted: an owner frees its memory by going
+// away, not through a list of pointers someone has to keep complete (tests/test_api_buffers.py).
+struct OrbBlock {
+    enum Kind { Device, Host };
+    explicit OrbBlock(Kind k = Device) : kind(k) {}
+    OrbBlock(OrbBlock &&o) noexcept : kind(o.kind), p(o.p), cap(o.cap) { o.p = nullptr, o.cap = 0; }
+    OrbBlock &operator=(OrbBlock &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            kind = o.kind, p = o.p, cap = o.cap;
+            o.p = nullptr, o.cap = 0;
+        }
+        return *this;
+    }
+    ~OrbBlock() { reset(); }
+    void reset()
+    {
+        if (p) (void)release();
+        p = nullptr, cap = 0;
+    }
+    // At least `need` bytes: when the block held is smaller, or there is none, it is freed and `alloc` bytes (16 for 0) take its
+    // place -- contents are not kept.  *moved (when given) reports that the block was replaced, i.e. its address changed.
+    hipError_t grow(size_t need, size_t alloc, bool *moved = nullptr)
+    {
+        if (moved) *moved = false;
+        if (p && need <= cap) return hipSuccess;
+        if (p) {
+            if (const hipError_t e = release()) return e;
+            p = nullptr, cap = 0;
+        }
+        if (moved) *moved = true;
+        void *q = nullptr;
+        if (const hipError_t e = kind == Host ? hipHostMalloc(&q, alloc ? alloc : 16, hipHostMallocDefault)
+                                              : hipMalloc(&q, alloc ? alloc : 16))
+            return e;
+        p = q, cap = alloc;
+        return hipSuccess;
+    }
+    hipError_t grow(size_t need) { return grow(need, need); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+    size_t bytes() const { return cap; }
+    explicit operator bool() const { return p != nullptr; }
+
+private:
+    hipError_t release() { return kind == Host ? hipHostFree(p) : hipFree(p); }
+    Kind kind;
+    void *p = nullptr;
+    size_t cap = 0;
+};
+
+// A single-frame chain captured as one hipGraph (orbhip_extract's and orbhip_frame_build's; orb_graph_run, api_extract.hip).
+struct OrbGraph {
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    std::vector<uint8_t> key;   // the caller's replay key at capture time (sizes, parameters, the buffers the nodes hold)
+    unsigned long gen = 0;      // the context's allocGen at capture time
+    unsigned calls = 0;
+    void release()
+    {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr, graph = nullptr;
+        key.clear();
+    }
+};
+
 // Host-fed pipeline (orbhip_pipe_*): a ring of `depth` device input slots and device / pinned-host output slots, a
 // copy-in and a copy-out stream beside the context's compute stream.
 struct OrbPipe {
     int depth = 0, B = 0, w = 0, h = 0, stride = 0, dcap = 0;
     size_t frameBytes = 0, inBytes = 0, outBytes = 0, koff = 0, doff = 0, coff = 0;
     hipStream_t sIn = nullptr, sOut = nullptr;
-    std::vector<uint8_t *> d_in, d_out;         // `depth` device slots
-    std::vector<uint8_t *> h_out;               // depth + 1 page-locked result blocks (batch n -> block n % (depth + 1)): no
+    std::vector<OrbBlock> d_in, d_out;          // `depth` device slots
+    std::vector<OrbBlock> h_out;                // depth + 1 page-locked result blocks (batch n -> block n % (depth + 1)): no
                                                 // submit that the ring admits overwrites the block the last wait returned
     std::vector<hipEvent_t> evIn, evK, evOut;
     std::vector<int> slotB;
@@ -198,11 +266,42 @@ struct OrbPipe {
     int levelsup = 4, check_ori = 1;
     float nnratio = 0.7f;
     size_t m12off = 0, m21off = 0, nmoff = 0;   // inside an output slot, behind the counts
-    uint8_t *d_bowScratch = nullptr;            // word | weight | node, B * dcap entries each
+    OrbBlock d_bowScratch;                      // word | weight | node, B * dcap entries each
     int lastWaited = -1;                        // host result block of the batch the last orbhip_pipe_wait returned
 };
 
-struct orbhip_ctx {
+// The buffers of a context: orbhip_destroy frees them all at once (orbhip_ctx derives from this struct, and a default-constructed
+// one is assigned to that part of it).  Element type and layout in the comments.
+struct OrbCtxBuffers {
+    OrbBlock d_lvl0;                   // uint8_t: own copy of level 0 (host API)    [B][h][stride0]
+    OrbBlock d_pyr;                    // uint8_t: levels 1.. of every frame         [B][pyrFrameBytes]
+    OrbBlock d_blur;                   // uint8_t: blurred levels 0..                [B][lvl0+pyr bytes]
+    OrbBlock d_cand;                   // uint32_t: candidate slots                  [B][totalCands]
+    OrbBlock d_cellCnt;                // uint16_t: per-cell counts                  [B][totalCells]
+    OrbBlock d_pts;                    // uint32_t: compact candidates               [B][totalPts]
+    OrbBlock d_pnode;                  // uint32_t: quadtree scratch                 [B][totalPts]
+    OrbBlock d_lvlCandCnt;             // int32_t: candidates per (frame, level)     [B][16]
+    OrbBlock d_lvlKp;                  // uint32_t: quadtree winners (packed)        [B][totalKps]
+    OrbBlock d_lvlKpCnt;               // int32_t: winners per (frame, level)        [B][16]
+    OrbBlock d_qtTables;               // uint8_t: quadtree node tables when they exceed the LDS (large per-level quotas)
+    OrbBlock d_lvlAngle;               // float: orientation per winner              [B][totalKps]
+    OrbBlock d_kps;                    // the host API's results: keypoints | descriptors | counts [B][cap_out], carved per call
+    OrbBlock d_fastTiles;              // FastTile
+    OrbBlock d_blurTiles;              // BlurTile
+    OrbBlock d_chainTiles;             // ChainTile
+    OrbBlock d_blurBands;              // uint32_t, 6 x 64 x 16 bytes: the MFMA band operands of k_blur (blur_band_table)
+    OrbBlock d_resizeTab;              // int32_t, per level: x table [dw] int2, y table [dh] int4
+    OrbBlock d_match;                  // matching scratch
+    OrbBlock d_tmp;                    // staging block of the host-pointer entry points (grow-only; struct TmpDev, api_common.h)
+    OrbBlock d_maps;                   // float: rectification maps (orbhip_remap_set_maps), mapx then mapy, map_w * map_h each
+    // page-locked staging of the host API
+    OrbBlock h_stage{OrbBlock::Host};  // results
+    OrbBlock h_pack{OrbBlock::Host};   // page-locked twin of d_tmp for the small host-pointer calls (struct Packed, api_common.h)
+    OrbBlock h_in{OrbBlock::Host};     // input frames, rows s0 apart (orb_host_in_stage)
+    OrbBlock h_pyr{OrbBlock::Host};    // pyramid levels 1.. (hostPyr)
+};
+
+struct orbhip_ctx : OrbCtxBuffers {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // batches: the second quadtree half (and the blur of the two-kernel schedule)
@@ -229,39 +328,15 @@ struct orbhip_ctx {
     std::vector<ChainTile> chainTiles;            // chained pyramid of the single-frame path (empty = not available)
     std::vector<ChainGroup> chainGroups;
     ChainLevels chainLevels;
-    ChainTile *d_chainTiles = nullptr;
-    size_t cap_chainTiles = 0;
     size_t pyrFrameBytes = 0;      // bytes of one frame's levels 1..n-1 (level 0 separate)
     size_t lvl0FrameBytes = 0;
 
-    // device buffers (sized for max_w x max_h x max_batch at create time)
-    uint8_t *d_lvl0 = nullptr;     // own copy of level 0 (host API)          [B][h][stride0]
-    uint8_t *d_pyr = nullptr;      // levels 1.. of every frame               [B][pyrFrameBytes]
-    uint8_t *d_blur = nullptr;     // blurred levels 0..                      [B][lvl0+pyr bytes]
-    uint32_t *d_cand = nullptr;    // candidate slots                         [B][totalCands]
-    uint16_t *d_cellCnt = nullptr; // per-cell counts                         [B][totalCells]
-    uint32_t *d_pts = nullptr;     // compact candidates                      [B][totalPts]
-    uint32_t *d_pnode = nullptr;   // quadtree scratch                        [B][totalPts]
-    int32_t *d_lvlCandCnt = nullptr; // candidates per (frame, level)         [B][16]
-    uint32_t *d_lvlKp = nullptr;   // quadtree winners (packed)               [B][totalKps]
-    int32_t *d_lvlKpCnt = nullptr; // winners per (frame, level)              [B][16]
-    uint8_t *d_qtTables = nullptr; // quadtree node tables when they exceed the LDS (large per-level quotas)
-    size_t cap_qtTables = 0;
-    float *d_lvlAngle = nullptr;   // orientation per winner                  [B][totalKps]
-    orbhip_keypoint *d_kps = nullptr; // output staging (host API)            [B][outCap]
-    uint8_t *d_desc = nullptr;     //                                          [B][outCap][32]
-    int32_t *d_counts = nullptr;   //                                          [B]
-    FastTile *d_fastTiles = nullptr;
-    BlurTile *d_blurTiles = nullptr;
-    uint32_t *d_blurBands = nullptr;   // 6 x 64 x 16 bytes: the MFMA band operands of k_blur (blur_band_table)
-    int32_t *d_resizeTab = nullptr; // per level: x table [dw] int2, y table [dh] int4
+    // (the device buffers: OrbCtxBuffers, sized for max_w x max_h x max_batch at create time)
     size_t resizeTabOff[ORBHIP_MAX_LEVELS][3];   // column taps, row taps, 4-pixel groups (k_pyramid.hip)
     bool resizeGroups[ORBHIP_MAX_LEVELS] = {};
     ResizeFit resizeFit[ORBHIP_MAX_LEVELS];       // .ntx == 0: the level keeps k_resize<32>
     bool resizeHint[ORBHIP_MAX_LEVELS][2] = {};  // the computed source window is valid for 32-row / 8-row tiles    // the level has a group table (fast path of k_resize)
-    size_t cap_lvl0 = 0, cap_pyr = 0, cap_blur = 0, cap_cand = 0, cap_cells = 0, cap_pts = 0,
-           cap_kps = 0, cap_out = 0, cap_resize = 0, cap_fastTiles = 0, cap_blurTiles = 0,
-           cap_pnode = 0, cap_angle = 0, cap_cnt1 = 0, cap_cnt2 = 0, cap_cnt3 = 0;
+    size_t cap_out = 0;            // keypoints per frame that d_kps holds
 
     // state of the last extract call
     bool blurValid = false;        // d_blur holds the blurred pyramid of the last call (not after a batch through k_describe_blur)
@@ -270,38 +345,18 @@ struct orbhip_ctx {
     size_t last_frame0 = 0;
     int last_B = 0;
 
-    // pinned host staging for the host API
-    uint8_t *h_stage = nullptr;
-    size_t h_stage_bytes = 0;
-    uint8_t *h_pack = nullptr;        // page-locked twin of d_tmp for the small host-pointer calls (struct Packed, api_common.h)
-    size_t h_pack_bytes = 0;
     // the host-pointer call of a frame or two as ONE hipGraph launch (copy in, the twelve kernels, copy out): captured at the
     // first call of a geometry, replayed while (w, h, B, buffers) stay the same
-    uint8_t *h_in = nullptr;          // pinned input staging, rows s0 apart
-    size_t h_in_bytes = 0;
     // host copy of the pyramid levels 1.. (pinned), filled beside the kernels when orbhip_set_host_pyramid is on: the
     // drop-in's mvImagePyramid (Frame.cc:817) are headers into it and into h_in (level 0)
     bool hostPyr = false;
-    uint8_t *h_pyr = nullptr;
-    size_t h_pyr_bytes = 0;
     int h_pyr_B = 0;                  // frames of the last call that are valid in h_pyr (0 = none)
     bool h_in_valid = false;          // h_in holds the frames of the last call
     hipEvent_t evp[2] = {nullptr, nullptr};   // pyramid built | pyramid copied out
-    hipGraphExec_t g_exec = nullptr;
-    hipGraph_t g_graph = nullptr;
-    int g_w = 0, g_h = 0, g_B = 0;
+    OrbGraph graph;
     bool capturing = false;           // run_pipeline leaves the timing events out of a capture
-    unsigned g_calls = 0;
-    const void *g_key[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // d_lvl0, d_kps block, h_in, h_stage, h_pyr (or null) at capture time
-    unsigned long allocGen = 0;       // bumped whenever a device buffer of the context is reallocated (ensure())
-    unsigned long g_gen = 0;          // allocGen at capture time: part of the replay key (the kernel nodes hold d_pyr, d_cand, ...)
-
-    // matching scratch
-    void *d_match = nullptr;
-    size_t d_match_bytes = 0;
-    // staging block of the host-pointer entry points (grow-only; they used to hipMalloc / hipFree per call)
-    void *d_tmp = nullptr;
-    size_t d_tmp_bytes = 0;
+    unsigned long allocGen = 0;       // bumped whenever a pipeline buffer of the context is reallocated (ensure()): part of the
+                                      // replay key of both single-frame graphs (the kernel nodes hold d_pyr, d_cand, ...)
 
     // timing
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -310,14 +365,13 @@ struct orbhip_ctx {
     bool haveFastEvents = false;
     bool haveBlurEvents = false;   // evx[1] / evx[2] hold the blur launch of the last eager extract call with stage timing 2
 
-    // rectification maps (orbhip_remap_set_maps): mapx then mapy, map_w * map_h floats each
-    float *d_maps = nullptr;
+    // rectification maps (orbhip_remap_set_maps, d_maps)
     int map_w = 0, map_h = 0;
 
     // vocabulary
     OrbVocabDev voc;
     mutable std::mutex vocMutex;              // orders a load on this context against another thread's share / generation of it
-    std::shared_ptr<void> vocHold;            // the device block behind `voc`, shared by every context that borrowed it
+    std::shared_ptr<OrbBlock> vocHold;        // the device block behind `voc`, shared by every context that borrowed it
                                               // (orbhip_vocab_share): freed when the last of them lets go
 
     // host-fed pipeline

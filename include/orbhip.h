@@ -648,6 +648,83 @@ int orbhip_kfdb_detect_device(orbhip_ctx *ctx, int mode, int B, const void *d_qo
 int orbhip_kfdb_set_timing(orbhip_ctx *ctx, int on);
 int orbhip_kfdb_phase_times(orbhip_ctx *ctx, float *ms);
 
+/* ---- resident local map and Tracking::SearchLocalPoints (ref: src/Tracking.cc:2315-2365) ----
+ * What Frame::isInFrustum (src/Frame.cc:613-669) and ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th)
+ * (src/ORBmatcher.cc:45-129) read from a MapPoint lives on the device under a caller-chosen non-zero 64-bit key (the drop-in
+ * uses MapPoint::mnId + 1) and changes only when LocalMapping touches the point; a search sends a camera, a list of keys and
+ * one skip byte per point.  Results are bit for bit those of the reference's loops.
+ * Limits: max_points <= 16777216; a put that would exceed max_points returns ORBHIP_E_CAPACITY and leaves the store as it
+ * was; a key twice in one put / update_flags / erase call is ORBHIP_E_ARG; nlevels <= 16.  Nothing is truncated.  A put that
+ * fails with ORBHIP_E_HIP part way (points travel 4096 at a time) may leave keys in the store whose data never arrived: they are
+ * reported not in view until they are put again.  put / update_flags / erase synchronise the context's stream once per 4096 points.
+ * Divergences from the reference, by design: a point at the camera centre (dist == 0), one with a non-finite position,
+ * distance or mfMaxDistance / dist is reported not in view (the reference's int(ceil(inf)) is undefined); a key the store does
+ * not know is reported not in view.  The scale level comes from a threshold table built with the host's logf (below). */
+#define ORBHIP_MP_OBSERVED 1   /* MapPoint::Observations() > 0 */
+#define ORBHIP_MP_BAD 2        /* MapPoint::isBad() */
+/* A store for at most max_points map points; calling it again drops the old store.  clear forgets every point. */
+int orbhip_map_init(orbhip_ctx *ctx, int max_points);
+int orbhip_map_clear(orbhip_ctx *ctx);
+int orbhip_map_info(orbhip_ctx *ctx, int *live, int *capacity);
+/* Batched upsert: pos / normal = mWorldPos / mNormalVector [3n], min_dist / max_dist = the RAW mfMinDistance / mfMaxDistance
+ * (0.8f * / 1.2f * of GetMin/MaxDistanceInvariance are applied on the device: PredictScale reads the raw value),
+ * desc = GetDescriptor() [32n], flags = ORBHIP_MP_* [n]. */
+int orbhip_map_put(orbhip_ctx *ctx, int n, const uint64_t *keys, const float *pos, const float *normal, const float *min_dist,
+                   const float *max_dist, const uint8_t *desc, const uint8_t *flags);
+/* Flags of points already in the store (ORBHIP_E_ARG for a key that is not); erase forgets points (absent keys are no error). */
+int orbhip_map_update_flags(orbhip_ctx *ctx, int n, const uint64_t *keys, const uint8_t *flags);
+int orbhip_map_erase(orbhip_ctx *ctx, int n, const uint64_t *keys);
+/* The slots of keys, for orbhip_search_local_points_device: -1 for a key the store does not know.  A slot stays a point's
+ * until it is erased or the store is cleared. */
+int orbhip_map_slots(orbhip_ctx *ctx, int n, const uint64_t *keys, int32_t *slots);
+
+/* The frame's side of isInFrustum as the caller's Frame holds it: mRcw (row-major), mtcw, mOw; fx fy cx cy, mbf; mnMinX, mnMaxX,
+ * mnMinY, mnMaxY; mvScaleFactors[nlevels], mfLogScaleFactor, mnScaleLevels; the viewingCosLimit of the call (Tracking passes 0.5)
+ * and th.  level_ratio is the library's: T[k] = the smallest float r with logf(r) / log_scale_factor > (float)k, so that
+ * PredictScale's ceil(logf(ratio) / mfLogScaleFactor), clamped, is the number of k < nlevels - 1 with ratio >= T[k].
+ * orbhip_search_local_points fills it itself; for the _device form orbhip_local_camera_prepare does. */
+typedef struct {
+    float Rcw[9], tcw[3], Ow[3];
+    float fx, fy, cx, cy, mbf;
+    float min_x, max_x, min_y, max_y;
+    float scale_factors[16];
+    float log_scale_factor;
+    int32_t nlevels;
+    float viewing_cos_limit, th;
+    float level_ratio[15];
+    int32_t reserved;
+} orbhip_local_camera;
+/* What isInFrustum leaves in the MapPoint: mbTrackInView, mTrackProjX, mTrackProjY, mTrackProjXR, mnTrackScaleLevel,
+ * mTrackViewCos; all 0 for a point that is not in view (skipped, bad, unknown or rejected). */
+typedef struct {
+    float u, v, proj_xr, view_cos;
+    int32_t level, in_view;
+} orbhip_local_point;
+/* Fills cam->level_ratio from cam->log_scale_factor and cam->nlevels (cached per pair in the context).  The table builder
+ * checks what it assumes -- the predicate is false for the 4096 floats below T[k] and true for the 4096 from it -- and returns
+ * ORBHIP_E_ARG otherwise, or when log_scale_factor is not a positive finite number or nlevels is outside [1, 16]. */
+int orbhip_local_camera_prepare(orbhip_ctx *ctx, orbhip_local_camera *cam);
+/* The table alone (host only, no device needed; for tests): table[nlevels - 1]. */
+int orbhip_debug_predict_scale_table(float log_scale_factor, int nlevels, float *table);
+/* Replaces the second loop of Tracking::SearchLocalPoints and the SearchByProjection behind it.  The frame is the resident set
+ * frame_key, put with a grid (orbhip_set_put, orbhip_set_put_from_frame); frame_key 0 = a frame without features (the frustum
+ * test alone; match may be NULL).  u_right [n] or NULL, occupied [n] or NULL as in orbhip_search_by_projection.  keys [nq] in the
+ * order of mvpLocalMapPoints, skip[k] != 0 = mnLastFrameSeen == mCurrentFrame.mnId.  points [nq]; *n_to_match = the number of
+ * points in view; match [n] and *nmatches as orbhip_search_by_projection defines them (use_ratio = 1, check_ori = 0,
+ * TH_HIGH = 100): match[i] = index into keys.  One synchronisation per call; 5 bytes per local point cross the bus. */
+int orbhip_search_local_points(orbhip_ctx *ctx, uint64_t frame_key, const float *u_right, const uint8_t *occupied,
+                               const orbhip_local_camera *cam, const uint64_t *keys, const uint8_t *skip, int nq, float nnratio,
+                               orbhip_local_point *points, int *n_to_match, int32_t *match, int *nmatches);
+/* B frames laid out as for orbhip_search_by_projection_device, all against the one store: d_cam [B] (prepared),
+ * d_slots [B][cap_q] (orbhip_map_slots), d_skip [B][cap_q], d_nq [B]; d_points [B][cap_q], d_n_to_match [B], d_match [B][cap],
+ * d_nmatches [B].  No synchronisation.  Every d_cam record must have passed orbhip_local_camera_prepare (the kernel reads at
+ * most 16 levels whatever nlevels says). */
+int orbhip_search_local_points_device(orbhip_ctx *ctx, const void *d_kps_un, const void *d_desc, const void *d_counts, int cap,
+                                      int B, const void *d_u_right, const void *d_occupied, float min_x, float min_y, float inv_w,
+                                      float inv_h, const void *d_cell_off, const void *d_cell_idx, const void *d_cam,
+                                      const void *d_slots, const void *d_skip, const void *d_nq, int cap_q, float nnratio,
+                                      void *d_points, void *d_n_to_match, void *d_match, void *d_nmatches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,8 +39,8 @@ class KeyFrame;
 class MapPoint
 {
 public:
-    MapPoint() : mTrackProjX(0), mTrackProjY(0), mTrackProjXR(0), mbTrackInView(false), mnTrackScaleLevel(0),
-                 mTrackViewCos(0), nObs(0), mfMinDistance(0), mfMaxDistance(0), mpReplaced(0), mbBad(false) {}
+    MapPoint() : mnId(NextId()++), mTrackProjX(0), mTrackProjY(0), mTrackProjXR(0), mbTrackInView(false), mnTrackScaleLevel(0),
+                 mTrackViewCos(0), mnLastFrameSeen(0), nObs(0), mfMinDistance(0), mfMaxDistance(0), mpReplaced(0), mbBad(false) {}
     bool isBad() { return mbBad; }          // ref: include/MapPoint.h
     void SetBadFlag() { mbBad = true; }
     int Observations() { return nObs; }
@@ -64,6 +64,11 @@ public:
     MapPoint *GetReplaced() { return mpReplaced; }
     void SetDescriptor(const cv::Mat &d) { mDescriptor = d.clone(); }   // mDescriptor is protected in the reference
 
+    // ref: include/MapPoint.h "long unsigned int mnId; static long unsigned int nNextId;": mnId + 1 is the key under which
+    // LocalMapSearch keeps the point resident on the device
+    long unsigned int mnId;
+    static long unsigned int &NextId() { static long unsigned int n = 0; return n; }
+
     // Variables used by the tracking (ref: include/MapPoint.h:102-107), read by SearchByProjection
     float mTrackProjX;
     float mTrackProjY;
@@ -71,6 +76,7 @@ public:
     bool mbTrackInView;
     int mnTrackScaleLevel;
     float mTrackViewCos;
+    long unsigned int mnLastFrameSeen;       // ref: include/MapPoint.h (set by Tracking::SearchLocalPoints' first loop)
 
     // protected in the reference; the test programs fill them directly
     int nObs;

@@ -68,6 +68,17 @@ int orb_bow_rotation_check(const int32_t *pairs, int npairs, const int32_t *off1
 void orb_sets_release(orbhip_ctx *c);
 // api_kfdb.hip
 void orb_kfdb_release(orbhip_ctx *c);
+// api_localmap.hip
+void orb_localmap_release(orbhip_ctx *c);
+// api_sets.hip: what a search into a resident set with a grid needs of it (device pointers; false when there is no such set)
+struct OrbSetView {
+    int n;
+    float minX, minY, invW, invH;
+    const orbhip_keypoint *d_kps;
+    const uint8_t *d_desc;
+    const int32_t *d_cnt, *d_cellOff, *d_cellIdx;
+};
+bool orb_set_grid_view(orbhip_ctx *c, uint64_t key, OrbSetView *v);
 static inline bool grid_params_ok(float inv_w, float inv_h) { return inv_w > 0.f && inv_h > 0.f; }
 
 // Bump allocator over one temporary device block (host-pointer matching entry points).
@@ -150,6 +161,16 @@ struct Packed {
     {
         off = align_up(off, 256);
         if (bytes) memcpy(h + off, src, bytes);
+        void *p = d + off;
+        off += bytes;
+        inEnd = off;
+        return p;
+    }
+    // an input the caller fills in place: `bytes` bytes of the block, *host = where to write them, returns the device twin
+    void *in_reserve(size_t bytes, void **host)
+    {
+        off = align_up(off, 256);
+        *host = h + off;
         void *p = d + off;
         off += bytes;
         inEnd = off;

@@ -192,6 +192,7 @@ extern "C" void orbhip_destroy(orbhip_ctx *c)
     orb_pipe_release(c);
     orb_sets_release(c);
     orb_kfdb_release(c);
+    orb_localmap_release(c);
     c->graph.release();
     orb_frame_release(c);
     static_cast<OrbCtxBuffers &>(*c) = OrbCtxBuffers();   // every buffer, before the streams go

@@ -91,6 +91,14 @@ static OrbSet *find_set(orbhip_ctx *c, uint64_t key)
     return nullptr;
 }
 
+bool orb_set_grid_view(orbhip_ctx *c, uint64_t key, OrbSetView *v)
+{
+    OrbSet *s = find_set(c, key);
+    if (!s || !s->grid) return false;
+    *v = {s->n, s->minX, s->minY, s->invW, s->invH, s->d_kps, s->d_desc, s->d_cnt, s->d_cellOff, s->d_cellIdx};
+    return true;
+}
+
 extern "C" int orbhip_set_has(orbhip_ctx *c, uint64_t key, int n)
 {
     if (!c) return 0;

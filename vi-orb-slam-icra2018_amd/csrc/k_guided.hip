@@ -236,8 +236,17 @@ __device__ __forceinline__ void walk_window_rec(const GridParams &gp, const orbh
     }
 }
 
+// QIND (the local-map search, k_localmap.hip): a point's descriptor is row qslot[b][iq] of qdesc -- the resident map-point store --
+// instead of row [b][iq]; a point without a slot is never ORBHIP_Q_ACTIVE.
+template <bool QIND>
+__device__ __forceinline__ const uint4 *proj_qdesc(const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ qslot, size_t at)
+{
+    return reinterpret_cast<const uint4 *>(qdesc + (QIND ? (size_t)qslot[at] : at) * 32);
+}
+
 // candidate tuple: distance (9 bits) | octave << 9 (4 bits) | feature index << 13
-__global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__restrict__ kps,
+template <bool QIND>
+__device__ __forceinline__ void k_proj_cands_body(const orbhip_keypoint *__restrict__ kps,
                                                     const uint8_t *__restrict__ desc, int cap,
                                                     const float *__restrict__ uRight, const GridParams gp,
                                                     const int32_t *__restrict__ cellOff,
@@ -245,7 +254,7 @@ __global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__res
                                                     const orbhip_proj_query *__restrict__ queries,
                                                     const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
                                                     int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                    int32_t *__restrict__ tcount)
+                                                    int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
 {
     const int b = blockIdx.y, iq = blockIdx.x * 256 + threadIdx.x;
     if (iq >= capQpad) return;
@@ -253,7 +262,7 @@ __global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__res
     if (iq < min(nq[b], capQ)) {
         const orbhip_proj_query q = queries[(size_t)b * capQ + iq];
         if (q.flags & ORBHIP_Q_ACTIVE) {
-            const uint4 *qd = reinterpret_cast<const uint4 *>(qdesc + ((size_t)b * capQ + iq) * 32);
+            const uint4 *qd = proj_qdesc<QIND>(qdesc, qslot, (size_t)b * capQ + iq);
             const uint4 a0 = qd[0], a1 = qd[1];
             const uint4 *D = reinterpret_cast<const uint4 *>(desc + (size_t)b * cap * 32);
             const float *UR = uRight ? uRight + (size_t)b * cap : nullptr;
@@ -274,17 +283,44 @@ __global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__res
     tcount[(size_t)b * capQpad + iq] = count;
 }
 
+// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
+__global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__restrict__ kps,
+                                                    const uint8_t *__restrict__ desc, int cap,
+                                                    const float *__restrict__ uRight, const GridParams gp,
+                                                    const int32_t *__restrict__ cellOff,
+                                                    const float4 *__restrict__ rec,
+                                                    const orbhip_proj_query *__restrict__ queries,
+                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                    int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
+                                                    int32_t *__restrict__ tcount)
+{
+    k_proj_cands_body<false>(kps, desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, nullptr);
+}
+__global__ __launch_bounds__(256) void k_proj_cands_slot(const orbhip_keypoint *__restrict__ kps,
+                                                    const uint8_t *__restrict__ desc, int cap,
+                                                    const float *__restrict__ uRight, const GridParams gp,
+                                                    const int32_t *__restrict__ cellOff,
+                                                    const float4 *__restrict__ rec,
+                                                    const orbhip_proj_query *__restrict__ queries,
+                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                    int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
+                                                    int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
+{
+    k_proj_cands_body<true>(kps, desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
+}
+
 // The same lists for ONE frame per call: a 16-lane row per point instead of a thread.  A thread walks its window record by
 // record (20-40 dependent trips to memory: 85 us for the 1000 points of a frame, however few of them there are); a row reads
 // the cell ranges of up to 16 window columns at once, flattens them (row prefix sum) and examines 16 records per trip; the
 // records that pass keep their visiting order through a row ballot.  Same tuples, same counts.
-__global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
+template <bool QIND>
+__device__ __forceinline__ void k_proj_cands_row_body(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
                                                         const GridParams gp, const int32_t *__restrict__ cellOff,
                                                         const float4 *__restrict__ rec,
                                                         const orbhip_proj_query *__restrict__ queries,
                                                         const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
                                                         int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                        int32_t *__restrict__ tcount)
+                                                        int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
 {
     __shared__ int s_start[16][16], s_excl[16][17];
     const int b = blockIdx.y, tid = threadIdx.x, gl = tid & 15, row = tid >> 4;
@@ -295,7 +331,7 @@ __global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restric
         const orbhip_proj_query q = queries[(size_t)b * capQ + iq];
         int x0, x1, y0, y1;
         if ((q.flags & ORBHIP_Q_ACTIVE) && window_cells(gp, q.u, q.v, q.radius, x0, x1, y0, y1)) {
-            const uint4 *qd = reinterpret_cast<const uint4 *>(qdesc + ((size_t)b * capQ + iq) * 32);
+            const uint4 *qd = proj_qdesc<QIND>(qdesc, qslot, (size_t)b * capQ + iq);
             const uint4 a0 = qd[0], a1 = qd[1];
             const uint4 *D = reinterpret_cast<const uint4 *>(desc + (size_t)b * cap * 32);
             const float *UR = uRight ? uRight + (size_t)b * cap : nullptr;
@@ -343,6 +379,28 @@ __global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restric
         }
     }
     if (gl == 0) tcount[(size_t)b * capQpad + iq] = count;
+}
+
+// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
+__global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
+                                                        const GridParams gp, const int32_t *__restrict__ cellOff,
+                                                        const float4 *__restrict__ rec,
+                                                        const orbhip_proj_query *__restrict__ queries,
+                                                        const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                        int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
+                                                        int32_t *__restrict__ tcount)
+{
+    k_proj_cands_row_body<false>(desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, nullptr);
+}
+__global__ __launch_bounds__(256) void k_proj_cands_row_slot(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
+                                                        const GridParams gp, const int32_t *__restrict__ cellOff,
+                                                        const float4 *__restrict__ rec,
+                                                        const orbhip_proj_query *__restrict__ queries,
+                                                        const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                        int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
+                                                        int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
+{
+    k_proj_cands_row_body<true>(desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
 }
 
 // ---- per-query best feature of a KeyFrame window: the inner loop of ORBmatcher::Fuse (ref: src/ORBmatcher.cc:887-950 with
@@ -485,8 +543,8 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
     }
 }
 
-
-__global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__restrict__ kps,
+template <bool QIND>
+__device__ __forceinline__ void k_proj_assign_body(const orbhip_keypoint *__restrict__ kps,
                                                     const uint8_t *__restrict__ desc,
                                                     const int32_t *__restrict__ cnt, int cap,
                                                     const float *__restrict__ uRight,
@@ -499,7 +557,7 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
                                                     const int32_t *__restrict__ tcount, int32_t *__restrict__ qfeat,
                                                     int use_ratio, float nnratio, int check_ori, int th_high,
                                                     int32_t *__restrict__ match, int32_t *__restrict__ nmatches,
-                                                    const int32_t *__restrict__ fallback)
+                                                    const int32_t *__restrict__ fallback, const int32_t *__restrict__ qslot)
 {
     extern __shared__ uint32_t s_dyn[];
     __shared__ uint32_t s_tup[64 * PROJ_K];
@@ -645,7 +703,7 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
             } else {
                 // more candidates than the list holds: the reference's scan, identically in every lane
                 const orbhip_proj_query q = Q[base + j];
-                const uint4 *qd = reinterpret_cast<const uint4 *>(qdesc + ((size_t)b * capQ + base + j) * 32);
+                const uint4 *qd = proj_qdesc<QIND>(qdesc, qslot, (size_t)b * capQ + base + j);
                 const uint4 a0 = qd[0], a1 = qd[1];
                 walk_window(gp, q, K, O, I, [&](int idx, int oct) {
                     if ((s_occ[idx >> 5] >> (idx & 31)) & 1u) return;
@@ -737,6 +795,42 @@ __global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__res
     }
     for (int i = lane; i < cap; i += 64) match[(size_t)b * cap + i] = s_match[i];
     if (lane == 0) nmatches[b] = nm;
+}
+
+// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
+__global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__restrict__ kps,
+                                                    const uint8_t *__restrict__ desc,
+                                                    const int32_t *__restrict__ cnt, int cap,
+                                                    const float *__restrict__ uRight,
+                                                    const uint8_t *__restrict__ occupied, const GridParams gp,
+                                                    const int32_t *__restrict__ cellOff,
+                                                    const int32_t *__restrict__ cellIdx,
+                                                    const orbhip_proj_query *__restrict__ queries,
+                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                    int capQ, int capQpad, int keff, const uint32_t *__restrict__ tuples,
+                                                    const int32_t *__restrict__ tcount, int32_t *__restrict__ qfeat,
+                                                    int use_ratio, float nnratio, int check_ori, int th_high,
+                                                    int32_t *__restrict__ match, int32_t *__restrict__ nmatches,
+                                                    const int32_t *__restrict__ fallback)
+{
+    k_proj_assign_body<false>(kps, desc, cnt, cap, uRight, occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, nullptr);
+}
+__global__ __launch_bounds__(64) void k_proj_assign_slot(const orbhip_keypoint *__restrict__ kps,
+                                                    const uint8_t *__restrict__ desc,
+                                                    const int32_t *__restrict__ cnt, int cap,
+                                                    const float *__restrict__ uRight,
+                                                    const uint8_t *__restrict__ occupied, const GridParams gp,
+                                                    const int32_t *__restrict__ cellOff,
+                                                    const int32_t *__restrict__ cellIdx,
+                                                    const orbhip_proj_query *__restrict__ queries,
+                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
+                                                    int capQ, int capQpad, int keff, const uint32_t *__restrict__ tuples,
+                                                    const int32_t *__restrict__ tcount, int32_t *__restrict__ qfeat,
+                                                    int use_ratio, float nnratio, int check_ori, int th_high,
+                                                    int32_t *__restrict__ match, int32_t *__restrict__ nmatches,
+                                                    const int32_t *__restrict__ fallback, const int32_t *__restrict__ qslot)
+{
+    k_proj_assign_body<true>(kps, desc, cnt, cap, uRight, occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, qslot);
 }
 
 // ---- the same assignment for ONE frame per call (a frame or two per launch): parallel fixed point ----------------------
@@ -1489,7 +1583,7 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
                                 int B, const float *uRight, const uint8_t *occupied, float minX, float minY, float invW,
                                 float invH, const int32_t *cellOff, const int32_t *cellIdx, const orbhip_proj_query *queries,
                                 const uint8_t *qdesc, const int32_t *nq, int capQ, int use_ratio, float nnratio,
-                                int check_ori, int th_high, int32_t *match, int32_t *nmatches, void *scratch)
+                                int check_ori, int th_high, int32_t *match, int32_t *nmatches, void *scratch, const int32_t *qslot)
 {
     const GridParams gp = {minX, minY, invW, invH};
     const int capQpad = (capQ + 63) / 64 * 64;
@@ -1500,12 +1594,21 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
     const int keff = proj_keff();
     hipLaunchKernelGGL(k_proj_records, dim3((cap + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, cap, cellOff, cellIdx, rec);
     static const bool seqOnly = ORB_TUNE("PROJ_SEQ", 0) != 0;
-    if (!seqOnly)   // a 16-lane row per point (written for the single-frame call; 512-frame batches gain 3-4 % from it too)
-        hipLaunchKernelGGL(k_proj_cands_row, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff, rec,
-                           queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
-    else
-        hipLaunchKernelGGL(k_proj_cands, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp,
-                           cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
+    if (!seqOnly) {   // a 16-lane row per point (written for the single-frame call; 512-frame batches gain 3-4 % from it too)
+        if (qslot)
+            hipLaunchKernelGGL(k_proj_cands_row_slot, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff,
+                               rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
+        else
+            hipLaunchKernelGGL(k_proj_cands_row, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff, rec,
+                               queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
+    } else {
+        if (qslot)
+            hipLaunchKernelGGL(k_proj_cands_slot, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp,
+                               cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
+        else
+            hipLaunchKernelGGL(k_proj_cands, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp,
+                               cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
+    }
     // the parallel fixed-point kernel first; frames it cannot do (a point with more than 32
     // candidates, no fixed point yet) are left to the sequential one through fallback[] (ORBHIP_PROJ_SEQ=1: sequential only)
     static const int maxRounds = ORB_TUNE("PROJ_ROUNDS", PAR_ROUNDS);   // tests force the hand-over with 1
@@ -1517,6 +1620,15 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
             (void)hipFuncSetAttribute((const void *)k_proj_assign_par, hipFuncAttributeMaxDynamicSharedMemorySize, (int)parLds);
         hipLaunchKernelGGL(k_proj_assign_par, dim3(B, 1, 1), dim3(1024, 1, 1), parLds, s, kps, cnt, cap, occupied, queries, nq, capQ,
                            capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, maxRounds);
+    }
+    if (qslot) {
+        if (proj_assign_lds(cap) > 32 * 1024)
+            (void)hipFuncSetAttribute((const void *)k_proj_assign_slot, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)proj_assign_lds(cap));
+        hipLaunchKernelGGL(k_proj_assign_slot, dim3(B, 1, 1), dim3(64, 1, 1), proj_assign_lds(cap), s, kps, desc, cnt, cap, uRight,
+                           occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat,
+                           use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, qslot);
+        return ORBHIP_OK;
     }
     if (proj_assign_lds(cap) > 32 * 1024)
         (void)hipFuncSetAttribute((const void *)k_proj_assign, hipFuncAttributeMaxDynamicSharedMemorySize,

@@ -380,6 +380,8 @@ struct orbhip_ctx : OrbCtxBuffers {
     void *setTable = nullptr;
     // key-frame database (api_kfdb.hip)
     void *kfdb = nullptr;
+    // resident map points (api_localmap.hip)
+    void *localMap = nullptr;
     // orbhip_frame_build (api_frame.hip): the Frame constructor's device work as one captured graph
     void *frameBuild = nullptr;
     long long describeMirror = 0;     // != 0 while orbhip_frame_build enqueues: k_describe<.., MIRROR> stores its results twice
@@ -511,7 +513,15 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
                                 int B, const float *uRight, const uint8_t *occupied, float minX, float minY, float invW,
                                 float invH, const int32_t *cellOff, const int32_t *cellIdx, const orbhip_proj_query *queries,
                                 const uint8_t *qdesc, const int32_t *nq, int capQ, int use_ratio, float nnratio,
-                                int check_ori, int th_high, int32_t *match, int32_t *nmatches, void *scratch);
+                                int check_ori, int th_high, int32_t *match, int32_t *nmatches, void *scratch,
+                                const int32_t *qslot = nullptr);   // qslot: qdesc rows by index (k_localmap.hip)
+// k_localmap.hip
+void launch_map_scatter(hipStream_t s, const int32_t *slot, const void *a, const void *b, const uint32_t *flags, const void *desc,
+                        int n, int maxPoints, void *geoA, void *geoB, uint32_t *mflags, void *mdesc);
+void launch_map_flags(hipStream_t s, const int32_t *slot, const uint32_t *flags, int n, int maxPoints, uint32_t *mflags);
+void launch_local_frustum(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
+                          const orbhip_local_camera *cams, const int32_t *slots, const uint8_t *skip, const int32_t *nq, int capQ,
+                          int B, orbhip_local_point *points, orbhip_proj_query *queries, int32_t *nToMatch);
 void launch_distinctive(hipStream_t s, const uint8_t *desc, const int32_t *off, int P, int32_t *best, int32_t *bestMedian);
 void launch_tri_match(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const uint8_t *skip1, const float *ur1,
                       const int32_t *off1, const int32_t *idx1, const orbhip_keypoint *kps2, const uint8_t *desc2,

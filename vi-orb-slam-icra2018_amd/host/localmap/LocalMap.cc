@@ -1,0 +1,176 @@
+// LocalMap.cc -- host side of ORB_SLAM2::LocalMapSearch (include/orbhip/LocalMap.h): marshals MapPoint / Frame members into
+// the orbhip_map_* / orbhip_search_local_points calls and writes the results back the way the reference's loops do
+// (ref: src/Tracking.cc:2336-2364, src/Frame.cc:613-669, src/ORBmatcher.cc:45-129).
+#include "LocalMap.h"
+
+#include <cstdint>
+#include <cstring>
+
+#include "hiperror.h"
+#include "orbhip.h"
+
+namespace ORB_SLAM2
+{
+
+namespace
+{
+int g_localmap_device = 0;
+
+inline uint64_t key_of(MapPoint *pMP) { return (uint64_t)pMP->mnId + 1; }
+inline uint8_t flags_of(MapPoint *pMP)
+{
+    return (uint8_t)((pMP->Observations() > 0 ? ORBHIP_MP_OBSERVED : 0) | (pMP->isBad() ? ORBHIP_MP_BAD : 0));
+}
+}  // namespace
+
+void LocalMapSearch::SetDevice(int device) { g_localmap_device = device; }
+
+LocalMapSearch::LocalMapSearch(int maxPoints) : mpCtx(NULL)
+{
+    mpCtx = orbhip_create(g_localmap_device, 50, 1.2f, 1, 20, 7, 128, 128, 1);   // the smallest context: only its stream is used
+    if (!mpCtx) {
+        hipdetail::Fail("LocalMapSearch (device context)", orbhip_last_error(NULL));
+        return;
+    }
+    if (orbhip_map_init(mpCtx, maxPoints) != ORBHIP_OK) {
+        hipdetail::Fail("LocalMapSearch (orbhip_map_init)", orbhip_last_error(mpCtx));
+        orbhip_destroy(mpCtx);
+        mpCtx = NULL;
+        return;
+    }
+    orbhip_set_limit(mpCtx, 4);   // the frames being tracked: a handful at a time
+}
+
+LocalMapSearch::~LocalMapSearch()
+{
+    if (mpCtx) orbhip_destroy(mpCtx);
+}
+
+void LocalMapSearch::Put(MapPoint *pMP) { Put(std::vector<MapPoint *>(1, pMP)); }
+
+void LocalMapSearch::Put(const std::vector<MapPoint *> &vpMPs)
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (!mpCtx || vpMPs.empty()) return;
+    const size_t n = vpMPs.size();
+    std::vector<uint64_t> keys(n);
+    std::vector<float> pos(3 * n), nrm(3 * n), mn(n), mx(n);
+    std::vector<uint8_t> desc(32 * n), fl(n);
+    for (size_t i = 0; i < n; i++) {
+        MapPoint *p = vpMPs[i];
+        keys[i] = key_of(p);
+        const cv::Mat P = p->GetWorldPos(), N = p->GetNormal(), d = p->GetDescriptor();
+        for (int k = 0; k < 3; k++) {
+            pos[3 * i + k] = P.at<float>(k, 0);
+            nrm[3 * i + k] = N.at<float>(k, 0);
+        }
+        // the raw mfMinDistance / mfMaxDistance: the accessors multiply by 0.8f / 1.2f (ref: src/MapPoint.cc:388-398), and
+        // both are exact to undo only by reading the members -- protected in the reference, so LocalMapSearch is a friend
+        // there
+        mn[i] = p->mfMinDistance;
+        mx[i] = p->mfMaxDistance;
+        memcpy(&desc[32 * i], d.ptr(0), 32);
+        fl[i] = flags_of(p);
+    }
+    if (orbhip_map_put(mpCtx, (int)n, keys.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), fl.data()) != ORBHIP_OK)
+        hipdetail::Fail("LocalMapSearch::Put", orbhip_last_error(mpCtx));
+}
+
+void LocalMapSearch::UpdateFlags(MapPoint *pMP)
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (!mpCtx) return;
+    const uint64_t key = key_of(pMP);
+    const uint8_t fl = flags_of(pMP);
+    if (orbhip_map_update_flags(mpCtx, 1, &key, &fl) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::UpdateFlags", orbhip_last_error(mpCtx));
+}
+
+void LocalMapSearch::Erase(MapPoint *pMP)
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (!mpCtx) return;
+    const uint64_t key = key_of(pMP);
+    if (orbhip_map_erase(mpCtx, 1, &key) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::Erase", orbhip_last_error(mpCtx));
+}
+
+void LocalMapSearch::Clear()
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (!mpCtx) return;
+    if (orbhip_map_clear(mpCtx) != ORBHIP_OK || orbhip_set_drop(mpCtx, 0) != ORBHIP_OK)
+        hipdetail::Fail("LocalMapSearch::Clear", orbhip_last_error(mpCtx));
+}
+
+int LocalMapSearch::SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &vpLocalMapPoints, float th, float viewingCosLimit,
+                                      int *nToMatch)
+{
+    std::unique_lock<std::mutex> lock(mMutex);
+    if (nToMatch) *nToMatch = 0;
+    if (!mpCtx) return 0;
+    const int n = F.N, nq = (int)vpLocalMapPoints.size();
+    if (nq == 0) return 0;
+    if (F.mnScaleLevels < 1 || F.mnScaleLevels > 16 || (int)F.mvScaleFactors.size() < F.mnScaleLevels)
+        return hipdetail::Fail("LocalMapSearch::SearchLocalPoints", "the frame has no scale pyramid (mnScaleLevels, mvScaleFactors)"), 0;
+
+    // the frame as a resident set with a grid, under Frame::mnId + 1: uploaded the first time the frame is searched
+    const uint64_t frameKey = n > 0 ? (uint64_t)F.mnId + 1 : 0;
+    if (n > 0 && !orbhip_set_has(mpCtx, frameKey, n)) {
+        std::vector<uint8_t> d((size_t)n * 32);
+        for (int i = 0; i < n; i++) memcpy(&d[(size_t)i * 32], F.mDescriptors.ptr(i), 32);
+        if (orbhip_set_put(mpCtx, frameKey, reinterpret_cast<const orbhip_keypoint *>(F.mvKeysUn.data()), d.data(), n, NULL, NULL, NULL,
+                           0, Frame::mnMinX, Frame::mnMinY, Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv) != ORBHIP_OK)
+            return hipdetail::Fail("LocalMapSearch::SearchLocalPoints (orbhip_set_put)", orbhip_last_error(mpCtx)), 0;
+    }
+
+    orbhip_local_camera cam;
+    memset(&cam, 0, sizeof cam);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) cam.Rcw[3 * r + c] = F.mTcw.at<float>(r, c);    // mRcw, mtcw (ref: Frame::UpdatePoseMatrices)
+        cam.tcw[r] = F.mTcw.at<float>(r, 3);
+    }
+    for (int r = 0; r < 3; r++) {   // mOw = -mRcw.t()*mtcw: one gemm with alpha = -1, summed in double, one rounding
+        double s = 0;
+        for (int k = 0; k < 3; k++) s += (double)cam.Rcw[3 * k + r] * (double)cam.tcw[k];
+        cam.Ow[r] = (float)(-1.0 * s);
+    }
+    cam.fx = Frame::fx, cam.fy = Frame::fy, cam.cx = Frame::cx, cam.cy = Frame::cy, cam.mbf = F.mbf;
+    cam.min_x = Frame::mnMinX, cam.max_x = Frame::mnMaxX, cam.min_y = Frame::mnMinY, cam.max_y = Frame::mnMaxY;
+    for (int l = 0; l < F.mnScaleLevels; l++) cam.scale_factors[l] = F.mvScaleFactors[l];
+    cam.log_scale_factor = F.mfLogScaleFactor;
+    cam.nlevels = F.mnScaleLevels;
+    cam.viewing_cos_limit = viewingCosLimit;
+    cam.th = th;
+
+    std::vector<uint64_t> keys(nq);
+    std::vector<uint8_t> skip(nq), occupied(n > 0 ? n : 1, 0);
+    for (int k = 0; k < nq; k++) {
+        keys[k] = key_of(vpLocalMapPoints[k]);
+        skip[k] = vpLocalMapPoints[k]->mnLastFrameSeen == F.mnId ? 1 : 0;     // ref: src/Tracking.cc:2342
+    }
+    for (int i = 0; i < n; i++)
+        if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) occupied[i] = 1;   // ref: src/ORBmatcher.cc:87-89
+    std::vector<orbhip_local_point> pts(nq);
+    std::vector<int32_t> match(n > 0 ? n : 1);
+    int ntm = 0, found = 0;
+    const int rc = orbhip_search_local_points(mpCtx, frameKey, (n > 0 && (int)F.mvuRight.size() == n) ? F.mvuRight.data() : NULL,
+                                              occupied.data(), &cam, keys.data(), skip.data(), nq, 0.8f, pts.data(), &ntm,
+                                              match.data(), &found);   // 0.8: the matcher Tracking constructs here
+    if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::SearchLocalPoints", orbhip_last_error(mpCtx)), 0;
+    for (int k = 0; k < nq; k++) {
+        MapPoint *p = vpLocalMapPoints[k];
+        if (skip[k] || p->isBad()) continue;                   // ref: :2342-2345 -- the loop does not touch these
+        p->mbTrackInView = pts[k].in_view != 0;                // ref: src/Frame.cc:615
+        if (!pts[k].in_view) continue;
+        p->mTrackProjX = pts[k].u;                             // ref: :661-666
+        p->mTrackProjXR = pts[k].proj_xr;
+        p->mTrackProjY = pts[k].v;
+        p->mnTrackScaleLevel = pts[k].level;
+        p->mTrackViewCos = pts[k].view_cos;
+    }
+    for (int i = 0; i < n; i++)
+        if (match[i] >= 0 && match[i] < nq) F.mvpMapPoints[i] = vpLocalMapPoints[match[i]];   // ref: src/ORBmatcher.cc:123
+    if (nToMatch) *nToMatch = ntm;
+    return found;
+}
+
+}  // namespace ORB_SLAM2

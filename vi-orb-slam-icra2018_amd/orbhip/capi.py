@@ -59,6 +59,9 @@ SYMBOLS = [
     "orbhip_set_info", "orbhip_set_fingerprint", "orbhip_set_fingerprint_rows", "orbhip_vocab_share", "orbhip_vocab_generation", "orbhip_set_limit", "orbhip_debug_roundtrip", "orbhip_debug_path_mask", "orbhip_frame_build", "orbhip_frame_fingerprint", "orbhip_set_put_from_frame",
     "orbhip_kfdb_init", "orbhip_kfdb_add", "orbhip_kfdb_erase", "orbhip_kfdb_clear", "orbhip_kfdb_set_covis", "orbhip_kfdb_info",
     "orbhip_kfdb_score", "orbhip_kfdb_detect", "orbhip_kfdb_detect_device", "orbhip_kfdb_set_timing", "orbhip_kfdb_phase_times",
+    "orbhip_map_init", "orbhip_map_clear", "orbhip_map_info", "orbhip_map_put", "orbhip_map_update_flags", "orbhip_map_erase",
+    "orbhip_map_slots", "orbhip_local_camera_prepare", "orbhip_debug_predict_scale_table", "orbhip_search_local_points",
+    "orbhip_search_local_points_device",
 ]
 
 
@@ -207,6 +210,18 @@ def load():
     L.orbhip_kfdb_detect_device.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32]
     L.orbhip_kfdb_set_timing.argtypes = [vp, i32]
     L.orbhip_kfdb_phase_times.argtypes = [vp, vp]
+    L.orbhip_map_init.argtypes = [vp, i32]
+    L.orbhip_map_clear.argtypes = [vp]
+    L.orbhip_map_info.argtypes = [vp, ip, ip]
+    L.orbhip_map_put.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbhip_map_update_flags.argtypes = [vp, i32, vp, vp]
+    L.orbhip_map_erase.argtypes = [vp, i32, vp]
+    L.orbhip_map_slots.argtypes = [vp, i32, vp, vp]
+    L.orbhip_local_camera_prepare.argtypes = [vp, vp]
+    L.orbhip_debug_predict_scale_table.argtypes = [f32, i32, vp]
+    L.orbhip_search_local_points.argtypes = [vp, u64, vp, vp, vp, vp, vp, i32, f32, vp, ip, vp, ip]
+    L.orbhip_search_local_points_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp,
+                                                    i32, f32, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -725,6 +725,61 @@ int orbhip_search_local_points_device(orbhip_ctx *ctx, const void *d_kps_un, con
                                       const void *d_slots, const void *d_skip, const void *d_nq, int cap_q, float nnratio,
                                       void *d_points, void *d_n_to_match, void *d_match, void *d_nmatches);
 
+/* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
+ * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
+ * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with
+ * imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) (:924-925) before Frame::ComputeStereoFromRGBD (ref: src/Frame.cc:987-1008)
+ * reads it at the keypoints.  Here the colour frame travels as it is and a kernel in front of the pyramid makes it grey; the
+ * depth map is read at the keypoints only and converted there.
+ *   grey   = (4899 R + 9617 G + 1868 B + 8192) >> 14, OpenCV 2.4's 8-bit RGB2Gray; alpha is ignored; packed pixels, R first
+ *            (ORBHIP_FMT_RGB, _RGBA) or B first (_BGR, _BGRA)
+ *   depth  d = raw * factor (ORBHIP_DEPTH_U16; ORBHIP_DEPTH_F32 when |factor - 1| > 1e-5, else d = raw) at
+ *            ((int)kps[i].x, (int)kps[i].y) -- the DISTORTED keypoint, truncated; d > 0: depth_out[i] = d,
+ *            u_right[i] = kps_un[i].x - mbf / d, otherwise both -1.  Each operation rounded to float on its own.
+ *            Divergence: a keypoint outside the depth map has no depth (the reference reads out of bounds).
+ * Errors (ORBHIP_E_ARG, nothing is written): an unknown format or depth type, stride < w * channels, a device pointer or stride
+ * that is not aligned as stated, a factor that is not finite. */
+enum { ORBHIP_FMT_GREY = 0, ORBHIP_FMT_RGB, ORBHIP_FMT_BGR, ORBHIP_FMT_RGBA, ORBHIP_FMT_BGRA };
+enum { ORBHIP_DEPTH_NONE = 0, ORBHIP_DEPTH_U16, ORBHIP_DEPTH_F32 };
+/* Replaces cvtColor(im, im, CV_RGB2GRAY) and its three siblings.  src: rows `stride` bytes apart, any alignment; dst: w bytes of
+ * each of h rows are written, nothing else.  format: one of the four colour formats. */
+int orbhip_grey(orbhip_ctx *ctx, const uint8_t *src, int w, int h, int stride, int format, uint8_t *dst, int dst_stride);
+/* B resident frames, frame b at d_src + b * frame_stride / d_dst + b * dst_frame_stride.  Both bases 4-byte aligned, all four
+ * strides multiples of 4: the output can feed orbhip_extract_batch_device.  Asynchronous on the context's stream. */
+int orbhip_grey_device(orbhip_ctx *ctx, const void *d_src, int B, int w, int h, int stride, size_t frame_stride, int format,
+                       void *d_dst, int dst_stride, size_t dst_frame_stride);
+/* orbhip_extract on a colour frame: the frame is staged and copied in as it is (3 or 4 bytes per pixel), the conversion is the
+ * first node of the same graph, the results are those of orbhip_extract on the grey image.  ORBHIP_FMT_GREY: orbhip_extract.
+ * With orbhip_set_host_pyramid on, level 0 of the host pyramid is the grey image (copied back: the caller never had it). */
+int orbhip_extract_color(orbhip_ctx *ctx, const uint8_t *img, int w, int h, int stride, int format, orbhip_keypoint *kps,
+                         uint8_t *desc, int cap, int *n_out, float timings_ms[3]);
+/* Replaces Frame::ComputeStereoFromRGBD and the convertTo in front of it.  Host arithmetic, n reads of the caller's map: ctx is
+ * used for the error text only and may be NULL.  depth: dw x dh, rows depth_stride bytes apart, ORBHIP_DEPTH_U16 or _F32. */
+int orbhip_rgbd_depth(orbhip_ctx *ctx, const orbhip_keypoint *kps, const orbhip_keypoint *kps_un, int n, const void *depth,
+                      int depth_type, int dw, int dh, int depth_stride, float factor, float mbf, float *u_right,
+                      float *depth_out);
+/* The same for B resident frames: d_kps / d_kps_un [B][cap], d_counts [B] (NULL: cap per frame), map b at
+ * d_depth + b * depth_frame_stride; d_u_right / d_depth_out [B][cap], rows from d_counts[b] on are left alone.  d_depth,
+ * depth_stride and depth_frame_stride aligned to the element (2 or 4 bytes).  Asynchronous on the context's stream, behind
+ * orbhip_grey_device, orbhip_extract_batch_device and orbhip_undistort_keypoints_device. */
+int orbhip_rgbd_depth_device(orbhip_ctx *ctx, const void *d_kps, const void *d_kps_un, const void *d_counts, int cap, int B,
+                             const void *d_depth, int depth_type, int dw, int dh, int depth_stride, size_t depth_frame_stride,
+                             float factor, float mbf, void *d_u_right, void *d_depth_out);
+/* orbhip_frame_build for an RGB-D frame: one graph, one synchronisation.  The colour frame is converted on the device as in
+ * orbhip_extract_color; the depth (a w x h map; ORBHIP_DEPTH_NONE: none, u_right / depth_out read -1 and may be NULL) is gathered on the host
+ * after the synchronisation -- n reads of the caller's map, where an upload would move the whole map.  Every other output, the
+ * resident block and orbhip_frame_fingerprint are those of orbhip_frame_build on the grey image. */
+typedef struct orbhip_frame_input {
+    const uint8_t *img;
+    int w, h, stride, format;
+    const void *depth;
+    int depth_type, depth_stride;
+    float depth_factor, mbf;
+} orbhip_frame_input;
+int orbhip_frame_build_rgbd(orbhip_ctx *ctx, const orbhip_frame_input *in, const orbhip_frame_params *fp, orbhip_keypoint *kps,
+                            orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out, int32_t *cell_off, int32_t *cell_idx,
+                            int32_t *word_id, float *weight, int32_t *node_id, float *u_right, float *depth_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,10 @@ public:
     ORBextractor(const ORBextractor &) = delete;
     ORBextractor &operator=(const ORBextractor &) = delete;
 
-    // ref: include/ORBextractor.h:77-79.  Mask is ignored, as in the reference.
+    // ref: include/ORBextractor.h:77-79.  Mask is ignored, as in the reference.  A superset of the reference, which asserts
+    // CV_8UC1: a CV_8UC3 / CV_8UC4 image is converted to grey on the device (orbhip_extract_color, orbhip_frame_build_rgbd) as
+    // cvtColor(..., CV_RGB2GRAY / CV_BGR2GRAY / CV_RGBA2GRAY / CV_BGRA2GRAY) converts it -- the cvtColor lines of
+    // Tracking::GrabImage* go away -- and mvImagePyramid[0] is then the grey image.  SetColorOrder: Tracking's mbRGB.
     void operator()( cv::InputArray image, cv::InputArray mask,
       std::vector<cv::KeyPoint>& keypoints,
       cv::OutputArray descriptors);
@@ -67,6 +70,7 @@ public:
     // Clone a level to keep it longer.  SetPyramidDownload(false) when the caller never reads it (monocular).
     std::vector<cv::Mat> mvImagePyramid;
     void SetPyramidDownload(bool on) { mbDownloadPyramid = on; }
+    void SetColorOrder(bool bRGB) { mbRGB = bRGB; }
 
     // device selection for multi-GPU processes (one process per GPU); default device 0
     static void SetDevice(int device);
@@ -124,6 +128,7 @@ private:
     orbhip_ctx *mpCtx;
     int mCtxW, mCtxH;
     bool mbDownloadPyramid;
+    bool mbRGB;           // channel order of CV_8UC3 / CV_8UC4 images: red first (true) or blue first (OpenCV's default)
     bool mbBadParams;     // the constructor arguments are outside what liborbhip runs: operator() reports and returns nothing
     std::vector<cv::KeyPoint> mvKpStage;
 

@@ -22,10 +22,14 @@
 typedef unsigned char uchar;
 
 #define CV_8U 0
+#define CV_16U 2
 #define CV_32F 5
 #define CV_CN_SHIFT 3
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn)-1) << CV_CN_SHIFT))
 #define CV_8UC1 CV_MAKETYPE(CV_8U, 1)
+#define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
+#define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
+#define CV_16UC1 CV_MAKETYPE(CV_16U, 1)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
 #define CV_PI 3.1415926535897932384626433832795
 
@@ -128,7 +132,7 @@ public:
     int depth() const { return flags & 7; }
     int channels() const { return (flags >> CV_CN_SHIFT) + 1; }
     size_t elemSize() const { return esz(flags); }
-    size_t step1() const { return step / (depth() == CV_32F ? 4 : 1); }
+    size_t step1() const { return step / (depth() == CV_32F ? 4 : depth() == CV_16U ? 2 : 1); }
     bool isContinuous() const { return step == (size_t)cols * elemSize(); }
     Size size() const { return Size(cols, rows); }
     Mat row(int y) const { return Mat(*this, Rect(0, y, cols, 1)); }
@@ -143,7 +147,10 @@ public:
     template <typename T> const T &at(int y, int x) const { return ((const T *)(data + (size_t)y * step))[x]; }
 
 private:
-    static size_t esz(int type) { return (size_t)((type & 7) == CV_32F ? 4 : 1) * (size_t)((type >> CV_CN_SHIFT) + 1); }
+    static size_t esz(int type)
+    {
+        return (size_t)((type & 7) == CV_32F ? 4 : (type & 7) == CV_16U ? 2 : 1) * (size_t)((type >> CV_CN_SHIFT) + 1);
+    }
     std::shared_ptr<uchar> buf_;
 };
 

@@ -54,8 +54,17 @@ int orb_graph_run(orbhip_ctx *c, OrbGraph &g, const void *key, size_t keyBytes, 
 int orb_host_stage(orbhip_ctx *c, size_t bytes);                  // page-locked result block c->h_stage of at least `bytes`
 int orb_host_pyr_stage(orbhip_ctx *c, int B, uint8_t **dst);      // page-locked pyramid copy (or nullptr when not asked for)
 int orb_host_in_stage(orbhip_ctx *c, size_t bytes, OrbGraph *also = nullptr);   // page-locked input c->h_in of at least `bytes`
+int orb_extract_host(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int format, orbhip_keypoint *kps,
+                     uint8_t *desc, int cap, int *n_out);
+// api_ingest.hip: a colour frame (ORBHIP_FMT_RGB .. _BGRA) in front of a single-frame chain
+int orb_format_channels(int format);                              // 1, 3 or 4; 0: no such format
+int orb_color_stage(orbhip_ctx *c, const uint8_t *img, int w, int h, int stride, int format);   // -> c->h_color, rows w * channels apart
+int orb_color_enqueue(orbhip_ctx *c, int w, int h, int format, int s0);   // copy in, k_grey -> c->d_lvl0 (hostPyr: and back to c->h_in)
 // api_frame.hip
 void orb_frame_release(orbhip_ctx *c);
+int orb_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int h, int stride, int format, const orbhip_frame_params *fp,
+                    orbhip_keypoint *kps, orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out, int32_t *cell_off,
+                    int32_t *cell_idx, int32_t *word_id, float *weight, int32_t *node_id);
 // api_pipe.hip / api_comm.hip: what orbhip_destroy releases
 void orb_pipe_release(orbhip_ctx *c);
 void orb_comm_release(orbhip_ctx *c);

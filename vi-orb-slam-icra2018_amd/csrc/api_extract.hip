@@ -558,8 +558,10 @@ int orb_graph_run(orbhip_ctx *c, OrbGraph &g, const void *key, size_t keyBytes, 
 // in, seven resize launches, FAST, quadtree, blur, describe, copy out -- is ONE hipGraph launch.  Issued one by one the twelve
 // launches cost the host ~3.5 us each and the device waits for them; the graph is captured from the very same call sequence
 // (run_pipeline) at the first call of a geometry and replayed afterwards.  ORBHIP_NO_GRAPH=1 keeps the eager sequence.
-static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int s0, size_t cbytes,
-                               size_t koff, size_t doff, size_t coff, int dcap)
+// A colour frame (format != ORBHIP_FMT_GREY, B == 1; orbhip_extract_color): it is staged and copied in as it is, and k_grey into
+// d_lvl0 is the first kernel node (orb_color_stage / orb_color_enqueue, api_ingest.hip).
+static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int format, int s0,
+                               size_t cbytes, size_t koff, size_t doff, size_t coff, int dcap)
 {
     const size_t inBytes = (size_t)B * c->lvl0FrameBytes;
     int rc;
@@ -568,7 +570,9 @@ static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B,
     uint8_t *hpyr = nullptr;
     if ((rc = orb_host_pyr_stage(c, B, &hpyr))) return rc;
     c->h_in_valid = false;
-    for (int b = 0; b < B; b++) {
+    const bool colour = format != ORBHIP_FMT_GREY;
+    if (colour && (rc = orb_color_stage(c, imgs[0], w, h, stride, format))) return rc;
+    for (int b = 0; b < B && !colour; b++) {
         if (!imgs[b]) return fail(c, ORBHIP_E_ARG, "orbhip_extract_batch: null image");
         uint8_t *dst = c->h_in.as<uint8_t>() + (size_t)b * c->lvl0FrameBytes;
         if (stride == s0)
@@ -576,20 +580,25 @@ static int extract_small_graph(orbhip_ctx *c, const uint8_t *const *imgs, int B,
         else
             for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * s0, imgs[b] + (size_t)y * stride, (size_t)w);
     }
-    const uintptr_t key[8] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)B, (uintptr_t)c->d_lvl0.as<void>(),
-                              (uintptr_t)c->d_kps.as<void>(),
-                              (uintptr_t)c->h_in.as<void>(), (uintptr_t)c->h_stage.as<void>(), (uintptr_t)hpyr};
+    const uintptr_t key[11] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)B, (uintptr_t)c->d_lvl0.as<void>(),
+                               (uintptr_t)c->d_kps.as<void>(),
+                               (uintptr_t)c->h_in.as<void>(), (uintptr_t)c->h_stage.as<void>(), (uintptr_t)hpyr,
+                               (uintptr_t)format, (uintptr_t)(colour ? c->h_color.as<void>() : nullptr),
+                               (uintptr_t)(colour ? c->d_color.as<void>() : nullptr)};
     // the describe kernel writes keypoints, descriptors and counts straight into the page-locked result block (posted PCIe
     // writes of a few dozen KB that overlap the kernel): no copy node behind it -- that node started 8 us after describe ended
     auto enqueue = [&]() -> int {
         uint8_t *out = c->h_stage.as<uint8_t>();
-        HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), inBytes, hipMemcpyHostToDevice, c->stream));
+        if (colour) {
+            if (const int e = orb_color_enqueue(c, w, h, format, s0)) return e;
+        } else
+            HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), inBytes, hipMemcpyHostToDevice, c->stream));
         return orb_run_pipeline(c, c->d_lvl0.as<uint8_t>(), s0, c->lvl0FrameBytes, B, (orbhip_keypoint *)(out + koff), out + doff,
                                 (int32_t *)(out + coff), dcap, hpyr);
     };
     if ((rc = orb_graph_run(c, c->graph, key, sizeof(key), enqueue, "graph capture of the single-frame chain failed: "))) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->h_in_valid = true;
+    c->h_in_valid = !colour || c->hostPyr;   // (a colour frame's level 0 comes back only when the host pyramid is asked for)
     c->h_pyr_B = hpyr ? B : 0;
     return ORBHIP_OK;
 }
@@ -599,6 +608,15 @@ extern "C" int orbhip_extract_batch(orbhip_ctx *c, const uint8_t *const *imgs, i
 {
     if (!c || !imgs || !kps || !desc || !n_out || cap <= 0 || stride < w)
         return fail(c, ORBHIP_E_ARG, "orbhip_extract_batch: bad argument");
+    return orb_extract_host(c, imgs, B, w, h, stride, ORBHIP_FMT_GREY, kps, desc, cap, n_out);
+}
+
+// orbhip_extract_batch behind its argument check; format != ORBHIP_FMT_GREY: one colour frame (orbhip_extract_color, which has
+// checked it)
+int orb_extract_host(orbhip_ctx *c, const uint8_t *const *imgs, int B, int w, int h, int stride, int format, orbhip_keypoint *kps,
+                     uint8_t *desc, int cap, int *n_out)
+{
+    const bool colour = format != ORBHIP_FMT_GREY;
     HIPCHK(c, orb_enter(c));
     const int s0 = (int)align_up((size_t)w, 64);
     int rc;
@@ -612,9 +630,13 @@ extern "C" int orbhip_extract_batch(orbhip_ctx *c, const uint8_t *const *imgs, i
     uint8_t *blk = reinterpret_cast<uint8_t *>(c->d_kps.as<uint8_t>());
     static const bool noGraph = ORB_SWITCH("NO_GRAPH", 0) != 0;
     if (B < 8 && !noGraph) {
-        if ((rc = extract_small_graph(c, imgs, B, w, h, stride, s0, cbytes, koff, doff, coff, dcap))) return rc;
+        if ((rc = extract_small_graph(c, imgs, B, w, h, stride, format, s0, cbytes, koff, doff, coff, dcap))) return rc;
     } else {
-        for (int b = 0; b < B; b++) {
+        if (colour) {
+            if ((rc = orb_color_stage(c, imgs[0], w, h, stride, format))) return rc;
+            if ((rc = orb_color_enqueue(c, w, h, format, s0))) return rc;
+        }
+        for (int b = 0; b < B && !colour; b++) {
             if (!imgs[b]) return fail(c, ORBHIP_E_ARG, "orbhip_extract_batch: null image");
             HIPCHK(c, hipMemcpy2DAsync(c->d_lvl0.as<uint8_t>() + (size_t)b * c->lvl0FrameBytes, s0, imgs[b], stride, w, h,
                                        hipMemcpyHostToDevice, c->stream));
@@ -629,6 +651,7 @@ extern "C" int orbhip_extract_batch(orbhip_ctx *c, const uint8_t *const *imgs, i
         if ((rc = orb_host_stage(c, coff + align_up(cbytes, 256)))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->h_stage.as<uint8_t>(), blk, coff + cbytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->h_in_valid = colour && c->hostPyr;
         c->h_pyr_B = hpyr ? B : 0;
     }
     memcpy(n_out, c->h_stage.as<uint8_t>() + coff, cbytes);

@@ -129,11 +129,15 @@ static int fb_enqueue(orbhip_ctx *c, OrbFrameBuild *F, const orbhip_frame_params
     return ORBHIP_OK;
 }
 
-extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int h, int stride, const orbhip_frame_params *fp,
-                                  orbhip_keypoint *kps, orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out,
-                                  int32_t *cell_off, int32_t *cell_idx, int32_t *word_id, float *weight, int32_t *node_id)
+// orbhip_frame_build, and orbhip_frame_build_rgbd (api_ingest.hip) with a colour frame: format != ORBHIP_FMT_GREY puts k_grey
+// in front of the chain (orb_color_stage / orb_color_enqueue), everything behind it is the same.
+int orb_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int h, int stride, int format, const orbhip_frame_params *fp,
+                    orbhip_keypoint *kps, orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out, int32_t *cell_off,
+                    int32_t *cell_idx, int32_t *word_id, float *weight, int32_t *node_id)
 {
-    if (!c || !img || !kps || !kps_un || !desc || !n_out || cap <= 0 || stride < w || !fp_ok(fp))
+    const bool colour = format != ORBHIP_FMT_GREY;
+    if (!c || !img || !kps || !kps_un || !desc || !n_out || cap <= 0 || stride < w * orb_format_channels(format) ||
+        !orb_format_channels(format) || !fp_ok(fp))
         return fail(c, ORBHIP_E_ARG, "orbhip_frame_build: bad argument");
     const bool undist = fp->ndist > 0 && fp->dist[0] != 0.0f;                  // ref: src/Frame.cc:750-754
     const bool grid = grid_params_ok(fp->inv_w, fp->inv_h);
@@ -181,7 +185,9 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
     if ((rc = orb_host_pyr_stage(c, 1, &hpyr))) return rc;
     c->h_in_valid = false;
     F->valid = false;
-    if (stride == s0)
+    if (colour) {
+        if ((rc = orb_color_stage(c, img, w, h, stride, format))) return rc;
+    } else if (stride == s0)
         memcpy(c->h_in.as<uint8_t>(), img, (size_t)s0 * (h - 1) + w);
     else
         for (int y = 0; y < h; y++) memcpy(c->h_in.as<uint8_t>() + (size_t)y * s0, img + (size_t)y * stride, (size_t)w);
@@ -203,25 +209,30 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
         HIPCHK(c, e);
     }
     auto enqueue = [&]() -> int {
-        HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), c->lvl0FrameBytes, hipMemcpyHostToDevice,
-                                 c->stream));
+        if (colour) {
+            if (const int e = orb_color_enqueue(c, w, h, format, s0)) return e;
+        } else
+            HIPCHK(c, hipMemcpyAsync(c->d_lvl0.as<uint8_t>(), c->h_in.as<uint8_t>(), c->lvl0FrameBytes, hipMemcpyHostToDevice,
+                                     c->stream));
         return fb_enqueue(c, F, *fp, s0, undist, grid, bow);
     };
     static const bool noGraph = ORB_SWITCH("NO_GRAPH", 0) != 0;
     if (noGraph) {
         rc = enqueue();
     } else {
-        uint8_t key[9 * sizeof(uintptr_t) + sizeof(*fp)];
-        const uintptr_t k[9] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)c->d_lvl0.as<void>(), (uintptr_t)F->d_blk.as<void>(),
-                                (uintptr_t)c->h_in.as<void>(), (uintptr_t)F->h_blk.as<void>(), (uintptr_t)hpyr,
-                                (uintptr_t)c->voc.desc, (uintptr_t)c->voc.gen};
+        uint8_t key[12 * sizeof(uintptr_t) + sizeof(*fp)];
+        const uintptr_t k[12] = {(uintptr_t)w, (uintptr_t)h, (uintptr_t)c->d_lvl0.as<void>(), (uintptr_t)F->d_blk.as<void>(),
+                                 (uintptr_t)c->h_in.as<void>(), (uintptr_t)F->h_blk.as<void>(), (uintptr_t)hpyr,
+                                 (uintptr_t)c->voc.desc, (uintptr_t)c->voc.gen, (uintptr_t)format,
+                                 (uintptr_t)(colour ? c->h_color.as<void>() : nullptr),
+                                 (uintptr_t)(colour ? c->d_color.as<void>() : nullptr)};
         memcpy(key, k, sizeof(k));
         memcpy(key + sizeof(k), fp, sizeof(*fp));
         rc = orb_graph_run(c, F->graph, key, sizeof(key), enqueue, "orbhip_frame_build: graph capture failed: ");
     }
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->h_in_valid = true;
+    c->h_in_valid = !colour || c->hostPyr;   // (a colour frame's level 0 comes back only when the host pyramid is asked for)
     c->h_pyr_B = hpyr ? 1 : 0;
     // results: the packed block -> the caller's arrays
     const uint8_t *H = F->h_blk.as<uint8_t>();
@@ -248,6 +259,14 @@ extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int 
     F->fp = *fp;
     F->fingerprint = orbhip_set_fingerprint(kps_un, desc, n);
     return ORBHIP_OK;
+}
+
+extern "C" int orbhip_frame_build(orbhip_ctx *c, const uint8_t *img, int w, int h, int stride, const orbhip_frame_params *fp,
+                                  orbhip_keypoint *kps, orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out,
+                                  int32_t *cell_off, int32_t *cell_idx, int32_t *word_id, float *weight, int32_t *node_id)
+{
+    return orb_frame_build(c, img, w, h, stride, ORBHIP_FMT_GREY, fp, kps, kps_un, desc, cap, n_out, cell_off, cell_idx, word_id,
+                           weight, node_id);
 }
 
 extern "C" uint64_t orbhip_frame_fingerprint(const orbhip_ctx *c)

@@ -299,6 +299,9 @@ struct OrbCtxBuffers {
     OrbBlock h_pack{OrbBlock::Host};   // page-locked twin of d_tmp for the small host-pointer calls (struct Packed, api_common.h)
     OrbBlock h_in{OrbBlock::Host};     // input frames, rows s0 apart (orb_host_in_stage)
     OrbBlock h_pyr{OrbBlock::Host};    // pyramid levels 1.. (hostPyr)
+    // colour input of orbhip_extract_color / orbhip_frame_build_rgbd (api_ingest.hip): the caller's frame, rows w * channels apart
+    OrbBlock h_color{OrbBlock::Host};  // page-locked staging
+    OrbBlock d_color;                  // its device twin, read by k_grey
 };
 
 struct orbhip_ctx : OrbCtxBuffers {
@@ -548,6 +551,12 @@ int launch_stereo(orbhip_ctx *L, orbhip_ctx *R, const orbhip_keypoint *kpsL, con
 int orb_vocab_parse(const uint8_t *blob, size_t nbytes, OrbVocabHost &V, std::string &err);
 void launch_vocab_transform(hipStream_t s, const OrbVocabDev &V, const uint8_t *desc, int n, int levelsup,
                             int32_t *word_id, float *weight, int32_t *node_id, const int32_t *cnt = nullptr);
+// k_ingest.hip: packed 8UC3 / 8UC4 -> grey (channels 3 or 4; bgr: the first byte is blue), and ComputeStereoFromRGBD per keypoint
+void launch_grey(hipStream_t s, const uint8_t *src, int B, int w, int h, int stride, size_t sframe, int channels, bool bgr,
+                 uint8_t *dst, int dstride, size_t dframe);
+void launch_rgbd_depth(hipStream_t s, const orbhip_keypoint *kps, const orbhip_keypoint *kpsUn, const int32_t *counts, int cap, int B,
+                       const void *depth, int depthType, int dw, int dh, size_t dstride, size_t dframe, float factor, float mbf,
+                       float *uRight, float *depthOut);
 hipError_t launch_bow_seq(hipStream_t s, const uint8_t *desc, const orbhip_keypoint *kps, const int32_t *counts,
                           const int32_t *node, const float *weight, const uint8_t *valid, int cap, int B, int lag, int th,
                           int th_mode, float nnratio, int check_ori, int32_t *match12, int32_t *match21,

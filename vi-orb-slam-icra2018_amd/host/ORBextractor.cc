@@ -13,6 +13,14 @@
 #include "hiperror.h"
 #include "orbhip.h"
 
+// The two colour entry points are bound weakly: the host classes built against a C ABI without them (the mock under
+// tests/native, which the ThreadSanitizer build links instead of liborbhip.so) still link, and a colour image then fails there
+// like any other device error.  Against liborbhip.so they always resolve.  The trade: a liborbhip_host.so loaded beside an
+// older liborbhip.so reports the missing colour input at the first colour frame instead of failing to load.  Two stubs in
+// that mock would let these two lines and the check in operator() go.
+#pragma weak orbhip_extract_color
+#pragma weak orbhip_frame_build_rgbd
+
 static_assert(sizeof(cv::KeyPoint) == sizeof(orbhip_keypoint), "cv::KeyPoint must be the 28-byte OpenCV layout");
 
 namespace ORB_SLAM2
@@ -27,7 +35,7 @@ ORBextractor::ORBextractor(int _nfeatures, float _scaleFactor, int _nlevels,
     nfeatures(_nfeatures), scaleFactor(_scaleFactor), nlevels(_nlevels),
     iniThFAST(_iniThFAST), minThFAST(_minThFAST),
     mTimeOfComputePyramid(0), mTimeOfComputeKeyPointsOctTree(0), mTimeOfComputeDescriptor(0),
-    mpCtx(nullptr), mCtxW(0), mCtxH(0), mbDownloadPyramid(true), mbBadParams(false),
+    mpCtx(nullptr), mCtxW(0), mCtxH(0), mbDownloadPyramid(true), mbRGB(false), mbBadParams(false),
     mbFrameBuild(false), mFbNDist(0), mFbLevelsup(-1), mpFbVoc(nullptr), mbFbVocShared(false), mnFbVocGen(0), mnBuiltN(-1), mbBuiltGrid(false),
     mbBuiltBoW(false)
 {
@@ -138,7 +146,10 @@ void ORBextractor::operator()( cv::InputArray _image, cv::InputArray _mask, std:
         return;                                              // ref: :1048-1049
 
     cv::Mat image = _image.getMat();
-    assert(image.type() == CV_8UC1 );                        // ref: :1052
+    assert(image.depth() == CV_8U && (image.channels() == 1 || image.channels() == 3 || image.channels() == 4));   // ref: :1052 asserts CV_8UC1
+    // what the reference's callers do in front of this call (ref: src/Tracking.cc:909-922): by channel count and mbRGB
+    const int format = image.channels() == 3 ? (mbRGB ? ORBHIP_FMT_RGB : ORBHIP_FMT_BGR)
+                     : image.channels() == 4 ? (mbRGB ? ORBHIP_FMT_RGBA : ORBHIP_FMT_BGRA) : ORBHIP_FMT_GREY;
 
     // every failure below leaves the caller with what the reference leaves for a frame without corners: no keypoints,
     // released descriptors (ref: :1080-1081) -- never an exception (hiperror.h)
@@ -147,6 +158,13 @@ void ORBextractor::operator()( cv::InputArray _image, cv::InputArray _mask, std:
     {
         _descriptors.release();
         hipdetail::Fail("ORBextractor::operator()", mbBadParams ? "constructed with parameters liborbhip rejects" : orbhip_last_error(nullptr));
+        return;
+    }
+
+    if (format != ORBHIP_FMT_GREY && !(orbhip_extract_color && orbhip_frame_build_rgbd))
+    {
+        _descriptors.release();
+        hipdetail::Fail("ORBextractor::operator()", "this liborbhip has no colour input");
         return;
     }
 
@@ -187,11 +205,25 @@ void ORBextractor::operator()( cv::InputArray _image, cv::InputArray _mask, std:
         mvBuiltWord.resize(cap);
         mvBuiltNode.resize(cap);
         mvBuiltWeight.resize(cap);
-        rc = orbhip_frame_build(mpCtx, image.data, image.cols, image.rows, (int)image.step, &fp,
-                                reinterpret_cast<orbhip_keypoint *>(mvKpStage.data()),
-                                reinterpret_cast<orbhip_keypoint *>(mvBuiltKeysUn.data()), descStage.data, cap, &n,
-                                grid ? mvBuiltCellOff.data() : nullptr, grid ? mvBuiltCellIdx.data() : nullptr,
-                                bow ? mvBuiltWord.data() : nullptr, bow ? mvBuiltWeight.data() : nullptr, bow ? mvBuiltNode.data() : nullptr);
+        if (format == ORBHIP_FMT_GREY)
+            rc = orbhip_frame_build(mpCtx, image.data, image.cols, image.rows, (int)image.step, &fp,
+                                    reinterpret_cast<orbhip_keypoint *>(mvKpStage.data()),
+                                    reinterpret_cast<orbhip_keypoint *>(mvBuiltKeysUn.data()), descStage.data, cap, &n,
+                                    grid ? mvBuiltCellOff.data() : nullptr, grid ? mvBuiltCellIdx.data() : nullptr,
+                                    bow ? mvBuiltWord.data() : nullptr, bow ? mvBuiltWeight.data() : nullptr, bow ? mvBuiltNode.data() : nullptr);
+        else
+        {
+            // a colour frame: the conversion is the first node of the same graph.  The depth stays with the Frame
+            // (Frame::ComputeStereoFromRGBD, host/rgbd/FrameRGBD.cc), which has the map; none is passed here.
+            orbhip_frame_input in;
+            in.img = image.data; in.w = image.cols; in.h = image.rows; in.stride = (int)image.step; in.format = format;
+            in.depth = nullptr; in.depth_type = ORBHIP_DEPTH_NONE; in.depth_stride = 0; in.depth_factor = 1.0f; in.mbf = 0.0f;
+            rc = orbhip_frame_build_rgbd(mpCtx, &in, &fp, reinterpret_cast<orbhip_keypoint *>(mvKpStage.data()),
+                                         reinterpret_cast<orbhip_keypoint *>(mvBuiltKeysUn.data()), descStage.data, cap, &n,
+                                         grid ? mvBuiltCellOff.data() : nullptr, grid ? mvBuiltCellIdx.data() : nullptr,
+                                         bow ? mvBuiltWord.data() : nullptr, bow ? mvBuiltWeight.data() : nullptr,
+                                         bow ? mvBuiltNode.data() : nullptr, nullptr, nullptr);
+        }
         if (rc == ORBHIP_OK)
         {
             mnBuiltN = n;
@@ -201,9 +233,12 @@ void ORBextractor::operator()( cv::InputArray _image, cv::InputArray _mask, std:
             if (orbhip_get_stage_times(mpCtx, ms) == ORBHIP_OK) { t[0] = ms[0]; t[1] = ms[1] + ms[2]; t[2] = ms[3] + ms[4]; }
         }
     }
-    else
+    else if (format == ORBHIP_FMT_GREY)
         rc = orbhip_extract(mpCtx, image.data, image.cols, image.rows, (int)image.step,
                             reinterpret_cast<orbhip_keypoint *>(mvKpStage.data()), descStage.data, cap, &n, t);
+    else
+        rc = orbhip_extract_color(mpCtx, image.data, image.cols, image.rows, (int)image.step, format,
+                                  reinterpret_cast<orbhip_keypoint *>(mvKpStage.data()), descStage.data, cap, &n, t);
     if (rc != ORBHIP_OK)
     {
         _descriptors.release();

@@ -62,6 +62,8 @@ SYMBOLS = [
     "orbhip_map_init", "orbhip_map_clear", "orbhip_map_info", "orbhip_map_put", "orbhip_map_update_flags", "orbhip_map_erase",
     "orbhip_map_slots", "orbhip_local_camera_prepare", "orbhip_debug_predict_scale_table", "orbhip_search_local_points",
     "orbhip_search_local_points_device",
+    "orbhip_grey", "orbhip_grey_device", "orbhip_extract_color", "orbhip_rgbd_depth", "orbhip_rgbd_depth_device",
+    "orbhip_frame_build_rgbd",
 ]
 
 
@@ -222,6 +224,12 @@ def load():
     L.orbhip_search_local_points.argtypes = [vp, u64, vp, vp, vp, vp, vp, i32, f32, vp, ip, vp, ip]
     L.orbhip_search_local_points_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp,
                                                     i32, f32, vp, vp, vp, vp]
+    L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
+    L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
+    L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]
+    L.orbhip_rgbd_depth.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, vp, vp]
+    L.orbhip_rgbd_depth_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, C.c_size_t, f32, f32, vp, vp]
+    L.orbhip_frame_build_rgbd.argtypes = [vp, vp, vp, vp, vp, vp, i32, ip, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -138,6 +138,12 @@ def load_photographs():
     (no network, no dataset).  Read where they lie at run time, never copied; [] when the packages or PIL are absent.
     Grey = (4899 R + 9617 G + 1868 B + 8192) >> 14, the fixed-point RGB -> grey of cv::cvtColor (ref: the grey conversion every
     frame goes through before the extractor sees it, src/Tracking.cc GrabImageMonocular)."""
+    return [((4899 * rgb[:, :, 0] + 9617 * rgb[:, :, 1] + 1868 * rgb[:, :, 2] + 8192) >> 14).astype(np.uint8)
+            for rgb in (p.astype(np.int32) for p in load_photographs_rgb())]
+
+
+def load_photographs_rgb():
+    """The same photographs as (H, W, 3) uint8 RGB arrays: colour input for the RGB-D path's tests (orbhip/rgbd.py)."""
     import os
     out = []
     try:
@@ -158,8 +164,7 @@ def load_photographs():
     for p in paths:
         if not os.path.exists(p):
             continue
-        rgb = np.asarray(Image.open(p).convert("RGB")).astype(np.int32)
-        out.append(((4899 * rgb[:, :, 0] + 9617 * rgb[:, :, 1] + 1868 * rgb[:, :, 2] + 8192) >> 14).astype(np.uint8))
+        out.append(np.ascontiguousarray(np.asarray(Image.open(p).convert("RGB")), np.uint8))
     return out
 
 

@@ -780,6 +780,47 @@ int orbhip_frame_build_rgbd(orbhip_ctx *ctx, const orbhip_frame_input *in, const
                             orbhip_keypoint *kps_un, uint8_t *desc, int cap, int *n_out, int32_t *cell_off, int32_t *cell_idx,
                             int32_t *word_id, float *weight, int32_t *node_id, float *u_right, float *depth_out);
 
+/* ---- the monocular initialiser's RANSAC hypotheses scored in one call (ref: src/Initializer.cc:305-468) ----
+ * Initializer::FindHomography / FindFundamental (:124-223) run mMaxIterations times "eight-point solve, then CheckHomography /
+ * CheckFundamental over all N matches" and keep the first iteration of largest score.  The hypotheses depend on mvSets alone, not
+ * on each other's scores: the caller computes all H21i / H12i / F21i first (the solves stay on the host, with the integrator's
+ * own SVD) and one call scores them all and names the two winners.
+ *   match12[n1]   what orbhip_search_for_initialization returns: a feature of frame 2, or a negative value for none.  The k-th
+ *                 non-negative entry is the reference's mvMatches12[k]; this ascending order is the order of every sum.
+ *   H21, H12      [nH][9] row-major float, the matrices CheckHomography is given; F21 [nF][9], CheckFundamental's.  Either count
+ *                 may be 0 and its pointers NULL.
+ *   sigma         the reference's mSigma (1.0); invSigmaSquare = (float)(1.0 / (double)(sigma * sigma)), the product in float.
+ *   scores        [nH + nF], H first (host form: may be NULL): each the float sum from 0.0f over the matches in ascending
+ *                 order, the term of image 1 before the term of image 2 (F: the l2 term before the l1 term), a term with
+ *                 chiSquare > th (H 5.991f, F 3.841f; both score with 5.991f - chiSquare) skipped.  A NaN chiSquare is not
+ *                 greater than th: it is added, as in the reference.  Every operation is rounded to float on its own, in the
+ *                 source's left-to-right order; 1.0 / x is one correctly rounded float division.
+ *   best[2]       H then F: `currentScore > score` from score = 0 in index order, i.e. the first hypothesis of largest score
+ *                 if that score is > 0 -- otherwise it = -1, score = 0.0f, ninliers = 0.  A NaN score never wins.
+ *   inliers       [2][n1] bytes, H then F: the winner's vbMatchesInliers scattered to frame-1 feature indices (0 for an unmatched
+ *                 feature and when there is no winner).
+ * N == 0 matches: every score 0.0f, no winner.  Limits: nH + nF <= 65535; device form B <= 65535.
+ * Errors (ORBHIP_E_ARG, nothing is written): a negative count, sigma not finite or not > 0, nH + nF > 65535, and in the host form
+ * a match12[i] >= n2 (divergence: the reference would read mvKeys2 out of bounds).  In the device form such an entry -- anything
+ * outside [0, d_cnt2[b]) -- counts as unmatched. */
+typedef struct orbhip_init_best {
+    float score;
+    int32_t it;
+    int32_t ninliers;
+} orbhip_init_best;
+/* One upload, three launches on the context's stream, one synchronisation. */
+int orbhip_init_score(orbhip_ctx *ctx, const orbhip_keypoint *kps1_un, int n1, const orbhip_keypoint *kps2_un, int n2,
+                      const int32_t *match12, const float *H21, const float *H12, int nH, const float *F21, int nF, float sigma,
+                      float *scores, orbhip_init_best *best, uint8_t *inliers);
+/* B problems, asynchronous on the context's stream: d_kps1_un [B][cap1] / d_kps2_un [B][cap2] keypoints with d_cnt1 / d_cnt2 [B]
+ * and d_match12 [B][cap1], laid out like the arguments and the output of orbhip_search_for_initialization_device, which it can
+ * follow without a copy; d_H21 / d_H12 [B][nH][9], d_F21 [B][nF][9]; d_scores [B][nH + nF] (required), d_best [B][2] records,
+ * d_inliers [B][2][cap1] bytes, of which the entries from d_cnt1[b] on are left untouched.  The same three launches with B in
+ * the grid.  Pointers 4-byte aligned (d_inliers: any). */
+int orbhip_init_score_device(orbhip_ctx *ctx, const void *d_kps1_un, const void *d_cnt1, int cap1, const void *d_kps2_un,
+                             const void *d_cnt2, int cap2, int B, const void *d_match12, const void *d_H21, const void *d_H12,
+                             int nH, const void *d_F21, int nF, float sigma, void *d_scores, void *d_best, void *d_inliers);
+
 #ifdef __cplusplus
 }
 #endif

@@ -557,6 +557,12 @@ void launch_grey(hipStream_t s, const uint8_t *src, int B, int w, int h, int str
 void launch_rgbd_depth(hipStream_t s, const orbhip_keypoint *kps, const orbhip_keypoint *kpsUn, const int32_t *counts, int cap, int B,
                        const void *depth, int depthType, int dw, int dh, size_t dstride, size_t dframe, float factor, float mbf,
                        float *uRight, float *depthOut);
+// k_initscore.hip: CheckHomography / CheckFundamental of nH + nF hypotheses for B problems -- pairs, scores, winners (three launches).
+// kps1 / kps2: (x, y) floats at the head of elements stride1 / stride2 bytes apart; scratch: init_score_scratch_bytes(B, cap1).
+size_t init_score_scratch_bytes(int B, int cap1);
+void launch_init_score(hipStream_t s, const void *kps1, int stride1, const int32_t *cnt1, int cap1, const void *kps2, int stride2,
+                       const int32_t *cnt2, int cap2, int B, const int32_t *match12, const float *H21, const float *H12, int nH,
+                       const float *F21, int nF, float invSigmaSquare, float *scores, void *best, uint8_t *inliers, void *scratch);
 hipError_t launch_bow_seq(hipStream_t s, const uint8_t *desc, const orbhip_keypoint *kps, const int32_t *counts,
                           const int32_t *node, const float *weight, const uint8_t *valid, int cap, int B, int lag, int th,
                           int th_mode, float nnratio, int check_ori, int32_t *match12, int32_t *match21,

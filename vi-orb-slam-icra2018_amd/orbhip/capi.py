@@ -64,6 +64,7 @@ SYMBOLS = [
     "orbhip_search_local_points_device",
     "orbhip_grey", "orbhip_grey_device", "orbhip_extract_color", "orbhip_rgbd_depth", "orbhip_rgbd_depth_device",
     "orbhip_frame_build_rgbd",
+    "orbhip_init_score", "orbhip_init_score_device",
 ]
 
 
@@ -230,6 +231,8 @@ def load():
     L.orbhip_rgbd_depth.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, vp, vp]
     L.orbhip_rgbd_depth_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, C.c_size_t, f32, f32, vp, vp]
     L.orbhip_frame_build_rgbd.argtypes = [vp, vp, vp, vp, vp, vp, i32, ip, vp, vp, vp, vp, vp, vp, vp]
+    L.orbhip_init_score.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
+    L.orbhip_init_score_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
     _lib = L
     return L
 

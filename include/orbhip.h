@@ -821,6 +821,64 @@ int orbhip_init_score_device(orbhip_ctx *ctx, const void *d_kps1_un, const void 
                              const void *d_cnt2, int cap2, int B, const void *d_match12, const void *d_H21, const void *d_H12,
                              int nH, const void *d_F21, int nF, float sigma, void *d_scores, void *d_best, void *d_inliers);
 
+/* ---- the inlier checks of the PnP and Sim3 RANSACs for M hypotheses at once (ref: src/PnPsolver.cc:308-339, :209-225;
+ * src/Sim3Solver.cc:340-403, :183-200) ----
+ * Tracking::Relocalization and LoopClosing::ComputeSim3 run, per candidate key frame, "draw a minimal set, solve it (EPnP / Horn),
+ * CheckInliers over all N correspondences, keep the best".  The solves stay on the host with the integrator's own SVD / eigen; the
+ * caller hands over the M hypotheses it has and gets every count and what the solver's bookkeeping would have kept.  The
+ * reference leaves its loop early, so a call only pays with the hypotheses the caller has: the calls are chunkable (best_in).
+ * Arithmetic, every operation rounded on its own in the source's left-to-right order:
+ *   PnP   R, t, fu, fv, uc, vc double; X, Y, Z, u, v, max_err float (max_err[i] = sigma2[i] * th2, a float product, the caller's).
+ *         Xc = (float)(((r00*X + r01*Y) + r02*Z) + t0) in double, Yc alike; invZc = (float)(1.0 / (((r20*X + r21*Y) + r22*Z) + t2)):
+ *         a double division rounded to float, not one float division; ue = uc + ((fu * (double)Xc) * (double)invZc), ve alike;
+ *         distX = (float)((double)u - ue), distY alike; error2 = (distX*distX) + (distY*distY) in float; inlier iff
+ *         error2 < max_err[i].  NaN and inf fail; there is no test on the sign of the depth.
+ *   Sim3  everything float; the caller prepares X3Dc1, X3Dc2, P1im1, P2im2 and max_err1 / max_err2 as Sim3Solver's constructor does
+ *         ((float)(9.210 * (double)sigma2); a fork that keeps them in a vector<size_t> passes (float)mvnMaxError1[i]).
+ *         Project(X, T, K): Pc[r] = (float)(s + (double)t[r]), s accumulated in double from 0.0 over k = 0, 1, 2 of
+ *         (double)R[r][k] * (double)X[k]; invz = 1.0f / Pc[2], one float division; x = Pc[0] * invz; u = (fx * x) + cx; y, v alike.
+ *         dist1 = P1im1[i] - Project(X3Dc2[i], T12, K1), dist2 = Project(X3Dc1[i], T21, K2) - P2im2[i] (float subtractions);
+ *         err = (float)(((double)d0*d0) + ((double)d1*d1)); inlier iff err1 < max_err1[i] && err2 < max_err2[i].
+ * Hypotheses: PnP Rt [M][12] double, R row-major then t; Sim3 T [M][24] float, the 3x4 block of mT12i then of mT21i, row-major.
+ * K1 / K2: {fx, fy, cx, cy}.  counts [M] (host forms: may be NULL): the inliers of every hypothesis.
+ * PnP rule: from best = best_in (0 on the first call), hypothesis h is a record iff counts[h] >= min_inliers && counts[h] > best,
+ * and then best = counts[h].  res = {n_records, best_out}; rec_idx / rec_cnt: the first min(n_records, R) records' indices
+ * (ascending) and counts, rec_flags [R][N] their inlier bytes; entries and rows from min(n_records, R) on are left untouched.
+ * Sim3 rule: from best = best_in, for each h: counts[h] >= best makes best = counts[h], best_it = h; if counts[h] > min_inliers as
+ * well, h is the winner and nothing after it is looked at.  res = {winner, ninliers, best_it, best_out}: winner -1 and ninliers 0
+ * when there is none, best_it -1 when no hypothesis of this call reached best_in; flags [N]: the winner's bytes, all 0 without one.
+ * Carry: one call over M hypotheses and the same hypotheses in consecutive chunks, best_out fed back as best_in and the indices
+ * offset, give the same records / winner (Sim3: the chunks end with the first that has a winner).
+ * N == 0: every count 0.  N < min_inliers is no error.  M == 0: no record / winner, best_out = best_in.
+ * Errors (ORBHIP_E_ARG, nothing is written): a negative count, off not non-decreasing, M > 65535, B > 65535, R < 1,
+ * min_inliers < 0. */
+typedef struct orbhip_pnp_result {
+    int32_t n_records, best_out;
+} orbhip_pnp_result;
+typedef struct orbhip_sim3_result {
+    int32_t winner, ninliers, best_it, best_out;
+} orbhip_sim3_result;
+/* One upload through the context's page-locked block, two launches, one synchronisation. */
+int orbhip_pnp_score(orbhip_ctx *ctx, const float *P3Dw, const float *P2D, const float *max_err, int N, double fu, double fv, double uc,
+                     double vc, const double *Rt, int M, int min_inliers, int best_in, int R, int32_t *counts, orbhip_pnp_result *res,
+                     int32_t *rec_idx, int32_t *rec_cnt, uint8_t *rec_flags);
+int orbhip_sim3_score(orbhip_ctx *ctx, const float *X3Dc1, const float *X3Dc2, const float *P1im1, const float *P2im2,
+                      const float *max_err1, const float *max_err2, int N, const float *K1, const float *K2, const float *T, int M,
+                      int min_inliers, int best_in, int32_t *counts, orbhip_sim3_result *res, uint8_t *flags);
+/* B problems of different sizes with M hypotheses each, asynchronous on the context's stream.  off [B + 1], min_inliers [B] and
+ * best_in [B] (NULL: all 0) are host arrays, read before the call returns; problem b owns the points off[b] .. off[b + 1] of the
+ * concatenated device arrays.  d_Rt [B][M][12] / d_T [B][M][24]; d_counts [B][M] (required), d_res [B] records, d_rec_idx /
+ * d_rec_cnt [B][R]; problem b's R flag rows of off[b + 1] - off[b] bytes start at byte R * off[b] of d_rec_flags; d_flags is
+ * indexed like the points.  All problems share the camera(s).  Pointers aligned to their elements (flags: any). */
+int orbhip_pnp_score_device(orbhip_ctx *ctx, const void *d_P3Dw, const void *d_P2D, const void *d_max_err, const int32_t *off, int B,
+                            double fu, double fv, double uc, double vc, const void *d_Rt, int M, const int32_t *min_inliers,
+                            const int32_t *best_in, int R, void *d_counts, void *d_res, void *d_rec_idx, void *d_rec_cnt,
+                            void *d_rec_flags);
+int orbhip_sim3_score_device(orbhip_ctx *ctx, const void *d_X3Dc1, const void *d_X3Dc2, const void *d_P1im1, const void *d_P2im2,
+                             const void *d_max_err1, const void *d_max_err2, const int32_t *off, int B, const float *K1,
+                             const float *K2, const void *d_T, int M, const int32_t *min_inliers, const int32_t *best_in,
+                             void *d_counts, void *d_res, void *d_flags);
+
 #ifdef __cplusplus
 }
 #endif

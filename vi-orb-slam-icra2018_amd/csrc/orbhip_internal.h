@@ -563,6 +563,20 @@ size_t init_score_scratch_bytes(int B, int cap1);
 void launch_init_score(hipStream_t s, const void *kps1, int stride1, const int32_t *cnt1, int cap1, const void *kps2, int stride2,
                        const int32_t *cnt2, int cap2, int B, const int32_t *match12, const float *H21, const float *H12, int nH,
                        const float *F21, int nF, float invSigmaSquare, float *scores, void *best, uint8_t *inliers, void *scratch);
+// k_ransac.hip: PnPsolver::CheckInliers / Sim3Solver::CheckInliers of M hypotheses for B problems -- counts, then the solver's
+// rule in hypothesis order (two launches).  The points of all problems are concatenated; par: off[B + 1] | min_inliers[B] | best_in[B].
+struct OrbPnpPoints {
+    const float *X, *uv, *maxErr;         // [n][3], [n][2], [n]
+    double fu, fv, uc, vc;
+};
+struct OrbSim3Points {
+    const float *X1, *X2, *p1, *p2, *maxErr1, *maxErr2;   // X3Dc1 / X3Dc2 [n][3], P1im1 / P2im2 [n][2], [n], [n]
+    float K1[4], K2[4];                   // fx, fy, cx, cy
+};
+void launch_pnp_score(hipStream_t s, const OrbPnpPoints &P, const double *Rt, int M, const int32_t *par, int B, int32_t *counts,
+                      int32_t *countsCopy, int R, int32_t *res, int32_t *recIdx, int32_t *recCnt, uint8_t *flags);
+void launch_sim3_score(hipStream_t s, const OrbSim3Points &P, const float *T, int M, const int32_t *par, int B, int32_t *counts,
+                       int32_t *countsCopy, int32_t *res, uint8_t *flags);
 hipError_t launch_bow_seq(hipStream_t s, const uint8_t *desc, const orbhip_keypoint *kps, const int32_t *counts,
                           const int32_t *node, const float *weight, const uint8_t *valid, int cap, int B, int lag, int th,
                           int th_mode, float nnratio, int check_ori, int32_t *match12, int32_t *match21,

@@ -65,6 +65,7 @@ SYMBOLS = [
     "orbhip_grey", "orbhip_grey_device", "orbhip_extract_color", "orbhip_rgbd_depth", "orbhip_rgbd_depth_device",
     "orbhip_frame_build_rgbd",
     "orbhip_init_score", "orbhip_init_score_device",
+    "orbhip_pnp_score", "orbhip_pnp_score_device", "orbhip_sim3_score", "orbhip_sim3_score_device",
 ]
 
 
@@ -233,6 +234,11 @@ def load():
     L.orbhip_frame_build_rgbd.argtypes = [vp, vp, vp, vp, vp, vp, i32, ip, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_init_score.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
     L.orbhip_init_score_device.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, f32, vp, vp, vp]
+    f64 = C.c_double
+    L.orbhip_pnp_score.argtypes = [vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.orbhip_pnp_score_device.argtypes = [vp, vp, vp, vp, vp, i32, f64, f64, f64, f64, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.orbhip_sim3_score.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.orbhip_sim3_score_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -725,6 +725,57 @@ int orbhip_search_local_points_device(orbhip_ctx *ctx, const void *d_kps_un, con
                                       const void *d_slots, const void *d_skip, const void *d_nq, int cap_q, float nnratio,
                                       void *d_points, void *d_n_to_match, void *d_match, void *d_nmatches);
 
+/* ---- Tracking::UpdateLocalMap on the resident store (ref: src/Tracking.cc:2367-2429) ----
+ * What the two loops of UpdateLocalMap read beside the points: KeyFrame::mvpMapPoints of every key frame, as a table of
+ * fixed-stride rows on the device under a caller-chosen non-zero 64-bit key (the drop-in uses KeyFrame::mnId + 1).  A row entry
+ * is a point key of the store above or 0 (no point); the table keeps the point's slot and the slot's generation, so an entry
+ * whose point was erased, cleared away, or whose slot went to another point resolves to nothing until it is set again.
+ *   orbhip_map_vote     the first loop of UpdateLocalKeyFrames (:2411-2429): how many of the frame's points each key frame holds;
+ *   orbhip_map_collect  UpdateLocalPoints (:2377-2400): the points of the given key frames, each once, in the reference's order;
+ *   orbhip_track_local_points  collect and orbhip_search_local_points as one call, the list never leaving the device.
+ * The graph step between vote and collect (:2431-2530: isBad, the maximum, neighbours, children, parents, the limit of 80) stays
+ * with the caller, on its own KeyFrame objects.  Everything is integer work: results are exact.
+ * Limits: max_kfs <= 65536, max_row <= 8192, max_kfs * (max_row + 1) <= 2^26 entries (8 bytes each; ORBHIP_E_ARG beyond);
+ * a full table is ORBHIP_E_CAPACITY; at most 2^24 row entries per collect (ORBHIP_E_SIZE).  A point key the store does not
+ * know, a point twice within one row, n > max_row, an index outside the row (its length is that of the last put) and a key
+ * frame the table does not know (put excepted) are ORBHIP_E_ARG.  A failed call changes nothing.  Nothing is truncated.
+ * kf_put / kf_set / kf_erase synchronise the context's stream once; vote, collect and the fused call once.
+ * Divergences from the reference, by design: the vote counts a key frame through its own row (equal to the observation map
+ * under the reference's invariant that (KF, idx) is an observation iff KF->mvpMapPoints[idx] is the point); key frames come
+ * back in ascending key order (the reference's map<KeyFrame*, int> iterates by heap address; docs/parity.md); a slot that has
+ * been freed 2^24 times is retired, so the store's usable capacity can fall below max_points by such slots. */
+/* A table of at most max_kfs rows of at most max_row entries; needs orbhip_map_init (which drops the table with the store);
+ * calling it again drops the old table.  Nothing is allocated afterwards but the grow-only scratch of collect (4 bytes per row
+ * entry of the largest call).  clear forgets every key frame. */
+int orbhip_map_kf_init(orbhip_ctx *ctx, int max_kfs, int max_row);
+int orbhip_map_kf_clear(orbhip_ctx *ctx);
+int orbhip_map_kf_info(orbhip_ctx *ctx, int *live, int *capacity, int *max_row);
+/* The whole row of a key frame (upsert): point_keys [n] = mvpMapPoints as keys, 0 = no point. */
+int orbhip_map_kf_put(orbhip_ctx *ctx, uint64_t kf_key, int n, const uint64_t *point_keys);
+/* Single entries of a row: AddMapPoint / EraseMapPointMatch (key 0) / ReplaceMapPointMatch.  idx [m], point_keys [m]. */
+int orbhip_map_kf_set(orbhip_ctx *ctx, uint64_t kf_key, int m, const int32_t *idx, const uint64_t *point_keys);
+/* Forgets a key frame; an absent key is no error. */
+int orbhip_map_kf_erase(orbhip_ctx *ctx, uint64_t kf_key);
+/* frame_point_keys [n] = mCurrentFrame.mvpMapPoints as keys (0 = NULL, repeats count as often as they occur; unknown, erased
+ * and ORBHIP_MP_BAD points vote for nothing).  kf_keys_out / counts_out [cap]: the key frames with a non-zero count in
+ * ascending key order; *nout = their number, ORBHIP_E_CAPACITY when it exceeds cap (the first cap are filled). */
+int orbhip_map_vote(orbhip_ctx *ctx, int n, const uint64_t *frame_point_keys, uint64_t *kf_keys_out, int32_t *counts_out, int cap,
+                    int *nout);
+/* kf_keys [nkf] in the order of mvpLocalKeyFrames (a key twice: its second copy adds nothing).  local_keys_out [cap] = the keys
+ * of mvpLocalMapPoints element for element: rows in the given order, each in feature-index order, empty, stale and
+ * ORBHIP_MP_BAD entries dropped, the first occurrence of a point kept.  *nlocal = their number, ORBHIP_E_CAPACITY when it
+ * exceeds cap (the first cap are filled). */
+int orbhip_map_collect(orbhip_ctx *ctx, int nkf, const uint64_t *kf_keys, uint64_t *local_keys_out, int cap, int *nlocal);
+/* orbhip_map_collect, then orbhip_search_local_points over that list with skip[k] = (local_keys_out[k] is in seen_keys [nseen]:
+ * the frame's own matches, mnLastFrameSeen == mCurrentFrame.mnId; keys the store does not know are ignored).  frame_key,
+ * u_right, occupied, cam, nnratio, n_to_match, match, nmatches as there; points [cap]; match[i] indexes local_keys_out.  One
+ * dependency chain, one result block, one synchronisation; 8 * nkf + 4 * nseen bytes, the camera and the frame's u_right /
+ * occupied go up.  ORBHIP_E_CAPACITY when *nlocal exceeds cap: the first cap keys are filled, nothing else is. */
+int orbhip_track_local_points(orbhip_ctx *ctx, uint64_t frame_key, const float *u_right, const uint8_t *occupied,
+                              const orbhip_local_camera *cam, int nkf, const uint64_t *kf_keys, int nseen, const uint64_t *seen_keys,
+                              float nnratio, uint64_t *local_keys_out, int cap, int *nlocal, orbhip_local_point *points,
+                              int *n_to_match, int32_t *match, int *nmatches);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

@@ -7,11 +7,14 @@
 #ifndef ORBHIP_LOCALMAP_H
 #define ORBHIP_LOCALMAP_H
 
+#include <map>
 #include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #ifdef ORBHIP_WITH_REFERENCE_HEADERS
 #include "Frame.h"
+#include "KeyFrame.h"
 #include "MapPoint.h"
 #else
 #include "slamlite.h"
@@ -39,7 +42,7 @@ public:
     void UpdateFlags(MapPoint *pMP);
     // after Replace and at the end of SetBadFlag
     void Erase(MapPoint *pMP);
-    // from Tracking::Reset
+    // from Tracking::Reset (with ClearKeyFrames() where key frames are kept here as well)
     void Clear();
 
     // Leaves F.mvpMapPoints and, for every point of vpLocalMapPoints that is neither bad nor already seen in this frame
@@ -49,12 +52,49 @@ public:
     int SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &vpLocalMapPoints, float th, float viewingCosLimit,
                           int *nToMatch);
 
+    // ---- Tracking::UpdateLocalMap on the device (orbhip_map_kf_*, orbhip_map_vote, orbhip_map_collect,
+    // orbhip_track_local_points) ----
+    // Room for maxKFs key frames of at most maxRow features; before the first PutKeyFrame (which otherwise takes 4096 x 2048).
+    void InitKeyFrames(int maxKFs, int maxRow);
+    // pKF->mvpMapPoints as it is now (key KeyFrame::mnId + 1): for every new key frame.  Of a point the vector holds twice
+    // only the index GetIndexInKeyFrame reports is kept; points that were never Put are left out.
+    void PutKeyFrame(KeyFrame *pKF);
+    // one entry: after AddMapPoint / ReplaceMapPointMatch (pMP) and EraseMapPointMatch (NULL)
+    void SetMapPoint(KeyFrame *pKF, size_t idx, MapPoint *pMP);
+    // at the end of KeyFrame::SetBadFlag.  From then on the key frame adds no points to a local map, also where a list made
+    // before still names it (the reference would read the mvpMapPoints that SetBadFlag leaves in the bad key frame).
+    void EraseKeyFrame(KeyFrame *pKF);
+    // from Tracking::Reset, beside Clear(): forgets every key frame and frees the table's rows
+    void ClearKeyFrames();
+    // UpdateLocalKeyFrames alone (vote + covisibility step), for a caller that goes on with TrackLocalPoints
+    void UpdateLocalKeyFrames(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, KeyFrame *&pReferenceKF);
+    // Tracking::UpdateLocalMap without SetReferenceMapPoints: the vote on the device, the covisibility step of
+    // UpdateLocalKeyFrames here on the caller's objects with keyframeCounter walked in ascending mnId order (the reference
+    // walks it by heap address) and children in ascending mnId order, UpdateLocalPoints on the device.  Leaves the three
+    // outputs, F.mvpMapPoints (bad points become NULL) and the mnTrackReferenceForFrame stamps as the reference does; when no
+    // key frame shares a point with F, vpLocalKeyFrames and pReferenceKF stay and the points are rebuilt from them, as there.
+    void UpdateLocalMap(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, std::vector<MapPoint *> &vpLocalMapPoints,
+                        KeyFrame *&pReferenceKF);
+    // UpdateLocalPoints and the second half of SearchLocalPoints as one device call: vpLocalMapPoints is rebuilt from
+    // vpLocalKeyFrames and searched; the points of F.mvpMapPoints with mnLastFrameSeen == F.mnId are skipped.  Everything
+    // else as SearchLocalPoints.
+    int TrackLocalPoints(Frame &F, const std::vector<KeyFrame *> &vpLocalKeyFrames, std::vector<MapPoint *> &vpLocalMapPoints, float th,
+                         float viewingCosLimit, int *nToMatch);
+
     // device of the objects constructed from now on (default 0)
     static void SetDevice(int device);
 
 protected:
+    bool EnsureKeyFrames();
+    bool VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, KeyFrame *&pReferenceKF);
+    bool CollectKeys(const std::vector<KeyFrame *> &vpKFs, std::vector<uint64_t> &kfKeys);
+
     orbhip_ctx *mpCtx;
     std::mutex mMutex;
+    std::unordered_map<uint64_t, MapPoint *> mPointOf;   // key -> the object, for the lists that come back as keys
+    std::map<uint64_t, KeyFrame *> mKeyFrameOf;
+    bool mbKeyFrames = false;
+    size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
 };
 
 }  // namespace ORB_SLAM2

@@ -77,6 +77,7 @@ public:
     int mnTrackScaleLevel;
     float mTrackViewCos;
     long unsigned int mnLastFrameSeen;       // ref: include/MapPoint.h (set by Tracking::SearchLocalPoints' first loop)
+    long unsigned int mnTrackReferenceForFrame = 0;   // ref: include/MapPoint.h (set by Tracking::UpdateLocalPoints)
 
     // protected in the reference; the test programs fill them directly
     int nObs;
@@ -242,6 +243,13 @@ public:
         if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
         return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
     }
+    // read and written by Tracking::UpdateLocalKeyFrames (ref: include/KeyFrame.h, src/Tracking.cc:2445-2527): the stamp that
+    // keeps a key frame from entering the local map twice, and the spanning tree (filled by the caller)
+    long unsigned int mnTrackReferenceForFrame = 0;
+    std::set<KeyFrame *> mspChildrens;
+    KeyFrame *mpParent = 0;
+    std::set<KeyFrame *> GetChilds() { return mspChildrens; }
+    KeyFrame *GetParent() { return mpParent; }
 };
 
 inline int MapPoint::PredictScale(const float &currentDist, KeyFrame *pKF)

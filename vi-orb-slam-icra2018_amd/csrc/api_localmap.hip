@@ -9,12 +9,32 @@
 #define MAP_MAX_POINTS (1 << 24)
 #define MAP_CHUNK 4096        // points per staged upload of put / update_flags / erase
 #define MP_LIVE 0x80u         // (k_localmap.hip)
+#define MP_GEN_SHIFT 8        // bits 8..31 of a flag word: the slot's generation (k_localcollect.hip)
+#define MP_GEN_END (1u << 24)
+#define KF_MAX_KFS (1 << 16)
+#define KF_MAX_ROW (1 << 13)
+#define KF_MAX_ENTRIES ((int64_t)1 << 26)   // 512 MB of rows
+#define KF_MAX_CALL (1u << 24)              // row entries per collect: 65536 block counts for the one-block scan
+
+// the key-frame -> map-point table (orbhip_map_kf_*): device rows (k_localcollect.hip) and their host mirror
+struct OrbKfTable {
+    int maxKfs = 0, maxRow = 0, stride = 0, rowHigh = 0;   // stride = maxRow + 1 entries; rows [0, rowHigh) have been used
+    OrbBlock rows, marks, first, scratch;                  // int2 [maxKfs][stride] | u32 [maxPoints] 0 | u32 [maxPoints] ~0 | collect
+    std::unordered_map<uint64_t, int32_t> rowOf;
+    std::vector<int32_t> freeRows;                         // (taken from the back: row 0 first)
+    std::vector<uint64_t> rowKey;                          // [maxKfs] 0 = free
+    std::vector<std::vector<uint64_t> > entries;           // [maxKfs] the row as uploaded: generation << 32 | slot, ~0 = no point
+};
 
 struct OrbLocalMap {
     int maxPoints = 0;
     OrbBlock geoA, geoB, flags, desc;              // [maxPoints] float4 {P, mfMinDistance} | float4 {normal, mfMaxDistance} | u32 | 32 B
     std::unordered_map<uint64_t, int32_t> slotOf;
     std::vector<int32_t> freeSlots;                // (taken from the back: slot 0 first)
+    std::vector<uint32_t> gen;                     // [maxPoints] how often the slot has been freed: bits 8..31 of its flag word
+    std::vector<uint64_t> slotKey;                 // [maxPoints] the key in the slot (0 = free)
+    OrbKfTable *kf = nullptr;
+    ~OrbLocalMap() { delete kf; }
     // the last threshold table (one (mfLogScaleFactor, mnScaleLevels) pair per SLAM session)
     bool tabValid = false;
     float tabLogS = 0.f;
@@ -32,9 +52,20 @@ void orb_localmap_release(orbhip_ctx *c)
 
 static void map_reset_table(OrbLocalMap *M)
 {
+    // every point that was in the store is gone: what a key-frame row still says about its slot must not resolve again
+    M->gen.resize(M->maxPoints, 0u);
+    M->slotKey.assign(M->maxPoints, 0);
+    for (const auto &kv : M->slotOf) M->gen[kv.second]++;
     M->slotOf.clear();
-    M->freeSlots.resize(M->maxPoints);
-    for (int i = 0; i < M->maxPoints; i++) M->freeSlots[i] = M->maxPoints - 1 - i;
+    M->freeSlots.clear();
+    M->freeSlots.reserve(M->maxPoints);
+    for (int i = M->maxPoints - 1; i >= 0; i--)
+        if (M->gen[i] < MP_GEN_END) M->freeSlots.push_back(i);   // (a slot whose generation count is used up is retired)
+}
+
+static inline uint32_t map_flag_word(const OrbLocalMap *M, int32_t slot, uint8_t flags)
+{
+    return MP_LIVE | (flags & (ORBHIP_MP_OBSERVED | ORBHIP_MP_BAD)) | (M->gen[slot] << MP_GEN_SHIFT);
 }
 
 extern "C" int orbhip_map_init(orbhip_ctx *c, int max_points)
@@ -129,11 +160,12 @@ extern "C" int orbhip_map_put(orbhip_ctx *c, int n, const uint64_t *keys, const 
                 s = M->freeSlots.back();
                 M->freeSlots.pop_back();
                 M->slotOf.emplace(keys[g], s);
+                M->slotKey[s] = keys[g];
             }
             hs[i] = s;
             ha[4 * i] = pos[3 * g], ha[4 * i + 1] = pos[3 * g + 1], ha[4 * i + 2] = pos[3 * g + 2], ha[4 * i + 3] = min_dist[g];
             hb[4 * i] = normal[3 * g], hb[4 * i + 1] = normal[3 * g + 1], hb[4 * i + 2] = normal[3 * g + 2], hb[4 * i + 3] = max_dist[g];
-            hf[i] = MP_LIVE | (flags[g] & (ORBHIP_MP_OBSERVED | ORBHIP_MP_BAD));
+            hf[i] = map_flag_word(M, s, flags[g]);
         }
         if ((rc = P.upload())) return rc;
         launch_map_scatter(c->stream, ds, da, db, df, dd, m, M->maxPoints, M->geoA.as<void>(), M->geoB.as<void>(),
@@ -176,7 +208,7 @@ extern "C" int orbhip_map_update_flags(orbhip_ctx *c, int n, const uint64_t *key
         auto it = M->slotOf.find(keys[i]);
         if (it == M->slotOf.end()) return fail(c, ORBHIP_E_ARG, "orbhip_map_update_flags: a key is not in the store");
         slots[i] = it->second;
-        words[i] = MP_LIVE | (flags[i] & (ORBHIP_MP_OBSERVED | ORBHIP_MP_BAD));
+        words[i] = map_flag_word(M, it->second, flags[i]);
     }
     if (has_duplicates(keys, n)) return fail(c, ORBHIP_E_ARG, "orbhip_map_update_flags: a key appears twice");
     return map_write_flags(c, M, slots, words);
@@ -200,7 +232,8 @@ extern "C" int orbhip_map_erase(orbhip_ctx *c, int n, const uint64_t *keys)
     for (int i = 0; i < n; i++) {
         auto it = M->slotOf.find(keys[i]);
         if (it == M->slotOf.end()) continue;
-        M->freeSlots.push_back(it->second);
+        M->slotKey[it->second] = 0;
+        if (++M->gen[it->second] < MP_GEN_END) M->freeSlots.push_back(it->second);
         M->slotOf.erase(it);
     }
     return ORBHIP_OK;
@@ -382,6 +415,417 @@ extern "C" int orbhip_search_local_points(orbhip_ctx *c, uint64_t frame_key, con
     memcpy(points, P.host(dp), (size_t)nq * sizeof(orbhip_local_point));
     if (n) memcpy(match, P.host(dm), (size_t)n * 4);
     const int32_t *hc = (const int32_t *)P.host(dc);
+    if (n_to_match) *n_to_match = hc[1];
+    if (nmatches) *nmatches = n ? hc[2] : 0;
+    return ORBHIP_OK;
+}
+
+// ---- the key-frame -> map-point table, the covisibility vote and the ordered point union ----
+#define KF_NONE (~(uint64_t)0)
+
+static inline uint64_t kf_pack(int32_t slot, uint32_t gen) { return ((uint64_t)gen << 32) | (uint32_t)slot; }
+// entry as the device reads it: int2 {slot, generation}, {-1, 0} for no point
+static inline void kf_unpack(uint64_t e, int32_t *dst)
+{
+    dst[0] = e == KF_NONE ? -1 : (int32_t)(uint32_t)e;
+    dst[1] = e == KF_NONE ? 0 : (int32_t)(uint32_t)(e >> 32);
+}
+
+static void kf_reset_table(OrbKfTable *K)
+{
+    K->rowOf.clear();
+    K->rowHigh = 0;
+    K->freeRows.resize(K->maxKfs);
+    for (int i = 0; i < K->maxKfs; i++) K->freeRows[i] = K->maxKfs - 1 - i;
+    K->rowKey.assign(K->maxKfs, 0);
+    K->entries.assign(K->maxKfs, std::vector<uint64_t>());
+}
+
+extern "C" int orbhip_map_kf_init(orbhip_ctx *c, int max_kfs, int max_row)
+{
+    if (!c || max_kfs <= 0 || max_kfs > KF_MAX_KFS || max_row <= 0 || max_row > KF_MAX_ROW ||
+        (int64_t)max_kfs * (max_row + 1) > KF_MAX_ENTRIES)
+        return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_init: bad argument");
+    OrbLocalMap *M = lmap(c);
+    if (!M) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_init: no store (orbhip_map_init)");
+    HIPCHK(c, orb_enter(c));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    delete M->kf;
+    M->kf = nullptr;
+    OrbKfTable *K = new OrbKfTable();
+    K->maxKfs = max_kfs, K->maxRow = max_row, K->stride = max_row + 1;
+    const size_t rowBytes = (size_t)max_kfs * K->stride * 8, slotBytes = (size_t)M->maxPoints * 4;
+    hipError_t e = K->rows.grow(rowBytes);
+    if (e == hipSuccess) e = K->marks.grow(slotBytes);
+    if (e == hipSuccess) e = K->first.grow(slotBytes);
+    if (e == hipSuccess) e = hipMemsetAsync(K->rows.as<void>(), 0, rowBytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(K->marks.as<void>(), 0, slotBytes, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(K->first.as<void>(), 0xFF, slotBytes, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        delete K;
+        return fail(c, ORBHIP_E_HIP, std::string("orbhip_map_kf_init: ") + hipGetErrorString(e));
+    }
+    kf_reset_table(K);
+    M->kf = K;
+    return ORBHIP_OK;
+}
+
+static OrbKfTable *kf_table(orbhip_ctx *c) { return lmap(c) ? lmap(c)->kf : nullptr; }
+
+extern "C" int orbhip_map_kf_clear(orbhip_ctx *c)
+{
+    if (!c) return ORBHIP_E_ARG;
+    OrbKfTable *K = kf_table(c);
+    if (!K) return ORBHIP_OK;
+    HIPCHK(c, orb_enter(c));
+    if (K->rowHigh > 0) HIPCHK(c, hipMemsetAsync(K->rows.as<void>(), 0, (size_t)K->rowHigh * K->stride * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    kf_reset_table(K);
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_map_kf_info(orbhip_ctx *c, int *live, int *capacity, int *max_row)
+{
+    if (!c) return ORBHIP_E_ARG;
+    OrbKfTable *K = kf_table(c);
+    if (live) *live = K ? (int)K->rowOf.size() : 0;
+    if (capacity) *capacity = K ? K->maxKfs : 0;
+    if (max_row) *max_row = K ? K->maxRow : 0;
+    return ORBHIP_OK;
+}
+
+// point key -> row entry; false for a key the store does not know
+static bool kf_resolve(const OrbLocalMap *M, uint64_t key, uint64_t *e)
+{
+    if (key == 0) return *e = KF_NONE, true;
+    auto it = M->slotOf.find(key);
+    if (it == M->slotOf.end()) return false;
+    return *e = kf_pack(it->second, M->gen[it->second]), true;
+}
+
+// header + entries of one row, from the page-locked block straight into the table
+static int kf_upload_row(orbhip_ctx *c, OrbKfTable *K, int row, const std::vector<uint64_t> &ent)
+{
+    HIPCHK(c, orb_enter(c));
+    const int n = (int)ent.size();
+    Packed P(c);
+    int rc;
+    if ((rc = P.begin((size_t)(n + 1) * 8 + 256))) return rc;
+    int32_t *h;
+    (void)P.in_reserve((size_t)(n + 1) * 8, (void **)&h);
+    h[0] = n, h[1] = 0;
+    for (int i = 0; i < n; i++) kf_unpack(ent[i], h + 2 + 2 * i);
+    HIPCHK(c, hipMemcpyAsync(K->rows.as<uint8_t>() + (size_t)row * K->stride * 8, h, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the page-locked block is reused by the next call)
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_map_kf_put(orbhip_ctx *c, uint64_t kf_key, int n, const uint64_t *point_keys)
+{
+    if (!c || kf_key == 0 || n < 0 || (n > 0 && !point_keys)) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_put: bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_put: no table (orbhip_map_kf_init)");
+    if (n > K->maxRow) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_put: more than max_row entries (orbhip_map_kf_init)");
+    std::vector<uint64_t> ent(n);
+    for (int i = 0; i < n; i++)
+        if (!kf_resolve(M, point_keys[i], &ent[i])) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_put: a point key is not in the store");
+    {
+        std::vector<uint64_t> k;
+        for (int i = 0; i < n; i++)
+            if (ent[i] != KF_NONE) k.push_back(ent[i]);
+        std::sort(k.begin(), k.end());
+        if (std::adjacent_find(k.begin(), k.end()) != k.end()) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_put: a point appears twice in the row");
+    }
+    auto it = K->rowOf.find(kf_key);
+    if (it == K->rowOf.end() && K->freeRows.empty())
+        return fail(c, ORBHIP_E_CAPACITY, "orbhip_map_kf_put: more than max_kfs key frames (orbhip_map_kf_init)");
+    const int row = it != K->rowOf.end() ? it->second : K->freeRows.back();
+    int rc;
+    if ((rc = kf_upload_row(c, K, row, ent))) return rc;
+    if (it == K->rowOf.end()) {
+        K->freeRows.pop_back();
+        K->rowOf.emplace(kf_key, row);
+        K->rowKey[row] = kf_key;
+        K->rowHigh = std::max(K->rowHigh, row + 1);
+    }
+    K->entries[row].swap(ent);
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_map_kf_set(orbhip_ctx *c, uint64_t kf_key, int m, const int32_t *idx, const uint64_t *point_keys)
+{
+    if (!c || kf_key == 0 || m < 0 || (m > 0 && (!idx || !point_keys))) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: no table (orbhip_map_kf_init)");
+    auto it = K->rowOf.find(kf_key);
+    if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: unknown key frame");
+    if (m == 0) return ORBHIP_OK;
+    const int row = it->second;
+    std::vector<uint64_t> ent = K->entries[row];   // the row as it will be
+    for (int j = 0; j < m; j++) {
+        if (idx[j] < 0 || idx[j] >= (int)ent.size()) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: an index outside the row");
+        if (!kf_resolve(M, point_keys[j], &ent[idx[j]])) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point key is not in the store");
+    }
+    for (int j = 0; j < m; j++) {   // (a later entry of the call may have emptied the index an earlier one filled: compare what stays)
+        const uint64_t e = ent[idx[j]];
+        if (e == KF_NONE) continue;
+        for (size_t i = 0; i < ent.size(); i++)
+            if (ent[i] == e && (int)i != idx[j]) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point appears twice in the row");
+    }
+    HIPCHK(c, orb_enter(c));
+    Packed P(c);
+    int rc;
+    if ((rc = P.begin((size_t)m * 16 + 2 * 256))) return rc;
+    int64_t *hat;
+    int32_t *hval;
+    const int64_t *dat = (const int64_t *)P.in_reserve((size_t)m * 8, (void **)&hat);
+    const void *dval = P.in_reserve((size_t)m * 8, (void **)&hval);
+    for (int j = 0; j < m; j++) {
+        hat[j] = (int64_t)row * K->stride + 1 + idx[j];
+        kf_unpack(ent[idx[j]], hval + 2 * j);   // (an index twice in one call: both lanes write the last value)
+    }
+    if ((rc = P.upload())) return rc;
+    launch_kf_set(c->stream, dat, dval, m, (int64_t)K->maxKfs * K->stride, K->rows.as<void>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    K->entries[row].swap(ent);
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_map_kf_erase(orbhip_ctx *c, uint64_t kf_key)
+{
+    if (!c) return ORBHIP_E_ARG;
+    OrbKfTable *K = kf_table(c);
+    if (!K) return ORBHIP_OK;
+    auto it = K->rowOf.find(kf_key);
+    if (it == K->rowOf.end()) return ORBHIP_OK;
+    const int row = it->second;
+    int rc;
+    if ((rc = kf_upload_row(c, K, row, std::vector<uint64_t>()))) return rc;   // the device forgets first
+    K->entries[row].clear();
+    K->rowKey[row] = 0;
+    K->freeRows.push_back(row);
+    K->rowOf.erase(it);
+    return ORBHIP_OK;
+}
+
+// slots of point keys for the mark scatters: -1 for 0 and for keys the store does not know
+static void kf_mark_slots(const OrbLocalMap *M, const uint64_t *keys, int n, int32_t *slots)
+{
+    for (int i = 0; i < n; i++) {
+        auto it = keys[i] ? M->slotOf.find(keys[i]) : M->slotOf.end();
+        slots[i] = it == M->slotOf.end() ? -1 : it->second;
+    }
+}
+
+extern "C" int orbhip_map_vote(orbhip_ctx *c, int n, const uint64_t *frame_point_keys, uint64_t *kf_keys_out, int32_t *counts_out,
+                               int cap, int *nout)
+{
+    if (!c || n < 0 || (n > 0 && !frame_point_keys) || cap < 0 || (cap > 0 && (!kf_keys_out || !counts_out)) || !nout)
+        return fail(c, ORBHIP_E_ARG, "orbhip_map_vote: bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, "orbhip_map_vote: no table (orbhip_map_kf_init)");
+    *nout = 0;
+    if (n == 0 || K->rowHigh == 0) return ORBHIP_OK;
+    HIPCHK(c, orb_enter(c));
+    const int R = K->rowHigh;
+    Packed P(c);
+    int rc;
+    if ((rc = P.begin((size_t)n * 4 + 16 + (size_t)R * 8 + 4 * 256))) return rc;
+    int32_t *hs;
+    const int32_t *ds = (const int32_t *)P.in_reserve((size_t)n * 4, (void **)&hs);
+    kf_mark_slots(M, frame_point_keys, n, hs);
+    const int32_t zero[4] = {0, 0, 0, 0};
+    int32_t *dout = (int32_t *)P.in(zero, 16);   // the count (comes back with the pairs behind it)
+    int32_t *dpairs = (int32_t *)P.out((size_t)R * 8);
+    if ((rc = P.upload())) return rc;
+    launch_mark_add(c->stream, ds, n, M->maxPoints, K->marks.as<uint32_t>());
+    launch_vote_rows(c->stream, K->rows.as<void>(), R, K->stride, K->maxRow, M->flags.as<uint32_t>(), M->maxPoints,
+                     K->marks.as<uint32_t>(), R, dout, dpairs);
+    launch_mark_clear(c->stream, ds, n, M->maxPoints, K->marks.as<uint32_t>());
+    HIPCHK(c, hipGetLastError());
+    if ((rc = P.download(dout))) return rc;
+    const int32_t *h = (const int32_t *)P.host(dpairs);
+    const int found = std::min(*(const int32_t *)P.host(dout), R);
+    std::vector<std::pair<uint64_t, int32_t> > v;
+    v.reserve(found);
+    for (int k = 0; k < found; k++) {
+        const int row = h[2 * k];
+        if (row >= 0 && row < K->maxKfs && K->rowKey[row]) v.push_back(std::make_pair(K->rowKey[row], h[2 * k + 1]));
+    }
+    std::sort(v.begin(), v.end());   // ascending key: the canonical order of the reference's map<KeyFrame*, int> (docs/parity.md)
+    *nout = (int)v.size();
+    for (int k = 0; k < (int)v.size() && k < cap; k++) kf_keys_out[k] = v[k].first, counts_out[k] = v[k].second;
+    if ((int)v.size() > cap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_map_vote: more key frames than cap (*nout has the number)");
+    return ORBHIP_OK;
+}
+
+// What a collect needs on the device: the rows of the call and their offsets, uploaded with the caller's block; the scratch
+struct KfCall {
+    uint32_t total = 0;   // candidates
+    const int32_t *d_rowIdx = nullptr;
+    const uint32_t *d_off = nullptr;
+    int32_t *d_cand = nullptr, *d_blockCnt = nullptr;
+    uint8_t *d_skip = nullptr;   // [capOut] (the fused call)
+};
+
+// validates the key frames and sizes the candidate list (no device work)
+static int kf_call_rows(orbhip_ctx *c, OrbKfTable *K, const char *who, int nkf, const uint64_t *kf_keys, std::vector<int32_t> &rowIdx,
+                        std::vector<uint32_t> &off)
+{
+    rowIdx.resize(nkf);
+    off.resize(nkf + 1);
+    uint64_t total = 0;
+    for (int k = 0; k < nkf; k++) {
+        auto it = K->rowOf.find(kf_keys[k]);
+        if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": unknown key frame");
+        rowIdx[k] = it->second;
+        off[k] = (uint32_t)total;
+        total += K->entries[it->second].size();
+        if (total > KF_MAX_CALL) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": more than 2^24 row entries in one call");
+    }
+    off[nkf] = (uint32_t)total;
+    return ORBHIP_OK;
+}
+
+static int kf_call_scratch(orbhip_ctx *c, OrbKfTable *K, KfCall &Q, int capOut)
+{
+    const size_t candBytes = align_up((size_t)Q.total * 4, 256), cntBytes = align_up((size_t)collect_blocks(Q.total) * 4, 256);
+    const size_t need = candBytes + cntBytes + (size_t)capOut + 256;
+    if (K->scratch.bytes() < need) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, K->scratch.grow(need, need + need / 2));
+    }
+    Q.d_cand = K->scratch.as<int32_t>();
+    Q.d_blockCnt = (int32_t *)(K->scratch.as<uint8_t>() + candBytes);
+    Q.d_skip = K->scratch.as<uint8_t>() + candBytes + cntBytes;
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_map_collect(orbhip_ctx *c, int nkf, const uint64_t *kf_keys, uint64_t *local_keys_out, int cap, int *nlocal)
+{
+    if (!c || nkf < 0 || (nkf > 0 && !kf_keys) || cap < 0 || (cap > 0 && !local_keys_out) || !nlocal)
+        return fail(c, ORBHIP_E_ARG, "orbhip_map_collect: bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, "orbhip_map_collect: no table (orbhip_map_kf_init)");
+    *nlocal = 0;
+    std::vector<int32_t> rowIdx;
+    std::vector<uint32_t> off;
+    int rc;
+    if ((rc = kf_call_rows(c, K, "orbhip_map_collect", nkf, kf_keys, rowIdx, off))) return rc;
+    KfCall Q;
+    Q.total = off[nkf];
+    if (Q.total == 0) return ORBHIP_OK;
+    HIPCHK(c, orb_enter(c));
+    const int capOut = (int)std::min<uint64_t>(Q.total, (uint64_t)cap);
+    if ((rc = kf_call_scratch(c, K, Q, capOut))) return rc;
+    Packed P(c);
+    if ((rc = P.begin((size_t)nkf * 8 + 4 + 16 + (size_t)capOut * 4 + 5 * 256))) return rc;
+    Q.d_rowIdx = (const int32_t *)P.in(rowIdx.data(), (size_t)nkf * 4);
+    Q.d_off = (const uint32_t *)P.in(off.data(), (size_t)(nkf + 1) * 4);
+    int32_t *dn = (int32_t *)P.out(256);          // the count | the slots, adjacent: one copy back
+    int32_t *dslots = (int32_t *)P.out((size_t)capOut * 4);
+    if ((rc = P.upload())) return rc;
+    launch_collect(c->stream, K->rows.as<void>(), K->rowHigh, K->stride, Q.d_rowIdx, Q.d_off, nkf, Q.total, M->flags.as<uint32_t>(),
+                   M->maxPoints, K->marks.as<uint32_t>(), K->first.as<uint32_t>(), Q.d_cand, Q.d_blockCnt, capOut, dslots, nullptr, dn);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = P.download(dn))) return rc;
+    const int got = *(const int32_t *)P.host(dn);
+    const int32_t *hs = (const int32_t *)P.host(dslots);
+    *nlocal = got;
+    for (int i = 0; i < got && i < capOut; i++) local_keys_out[i] = (hs[i] >= 0 && hs[i] < M->maxPoints) ? M->slotKey[hs[i]] : 0;
+    if (got > cap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_map_collect: more local points than cap (*nlocal has the number)");
+    return ORBHIP_OK;
+}
+
+extern "C" int orbhip_track_local_points(orbhip_ctx *c, uint64_t frame_key, const float *u_right, const uint8_t *occupied,
+                                         const orbhip_local_camera *cam, int nkf, const uint64_t *kf_keys, int nseen,
+                                         const uint64_t *seen_keys, float nnratio, uint64_t *local_keys_out, int cap, int *nlocal,
+                                         orbhip_local_point *points, int *n_to_match, int32_t *match, int *nmatches)
+{
+    if (!c || !cam || nkf < 0 || (nkf > 0 && !kf_keys) || nseen < 0 || (nseen > 0 && !seen_keys) || cap < 0 ||
+        (cap > 0 && (!local_keys_out || !points)) || !nlocal)
+        return fail(c, ORBHIP_E_ARG, "orbhip_track_local_points: bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, "orbhip_track_local_points: no table (orbhip_map_kf_init)");
+    OrbSetView S = {};
+    if (frame_key != 0) {
+        if (!orb_set_grid_view(c, frame_key, &S))
+            return fail(c, ORBHIP_E_ARG, "orbhip_track_local_points: unknown set, or a set without a grid (orbhip_set_put)");
+        if (!match) return fail(c, ORBHIP_E_ARG, "orbhip_track_local_points: bad argument");
+        if (S.n >= (1 << 19) || proj_assign_lds(S.n) > 120 * 1024)
+            return fail(c, ORBHIP_E_SIZE, "orbhip_track_local_points: the frame has too many features for the match table in LDS");
+    }
+    const int n = S.n;
+    orbhip_local_camera cm = *cam;
+    int rc;
+    if ((rc = orbhip_local_camera_prepare(c, &cm))) return rc;
+    std::vector<int32_t> rowIdx;
+    std::vector<uint32_t> off;
+    if ((rc = kf_call_rows(c, K, "orbhip_track_local_points", nkf, kf_keys, rowIdx, off))) return rc;
+    *nlocal = 0;
+    if (n_to_match) *n_to_match = 0;
+    if (nmatches) *nmatches = 0;
+    for (int i = 0; i < n; i++) match[i] = -1;
+    KfCall Q;
+    Q.total = off[nkf];
+    const int capQ = (int)std::min<uint64_t>(Q.total, (uint64_t)cap);
+    if (Q.total == 0) return ORBHIP_OK;
+    if (capQ == 0) {   // nothing can be returned: the count alone
+        uint64_t none;
+        return orbhip_map_collect(c, nkf, kf_keys, &none, 0, nlocal);
+    }
+    HIPCHK(c, orb_enter(c));
+    if ((rc = kf_call_scratch(c, K, Q, capQ))) return rc;
+    Packed P(c);
+    if ((rc = P.begin(sizeof cm + (size_t)nkf * 8 + 4 + (size_t)nseen * 4 + (size_t)n * (4 + 1 + 4) +
+                      (size_t)capQ * (4 + sizeof(orbhip_local_point)) + 16 * 256)))
+        return rc;
+    const void *dcam = P.in(&cm, sizeof cm);
+    Q.d_rowIdx = (const int32_t *)P.in(rowIdx.data(), (size_t)nkf * 4);
+    Q.d_off = (const uint32_t *)P.in(off.data(), (size_t)(nkf + 1) * 4);
+    int32_t *hseen;
+    const int32_t *dseen = (const int32_t *)P.in_reserve((size_t)nseen * 4, (void **)&hseen);
+    kf_mark_slots(M, seen_keys, nseen, hseen);
+    const float *dur = (n && u_right) ? (const float *)P.in(u_right, (size_t)n * 4) : nullptr;
+    const uint8_t *docc = (n && occupied) ? (const uint8_t *)P.in(occupied, (size_t)n) : nullptr;
+    const int32_t cnts[4] = {0, 0, 0, 0};
+    int32_t *dc = (int32_t *)P.in(cnts, 16);   // local points | points in view | matches (come back with what follows)
+    int32_t *dslots = (int32_t *)P.out((size_t)capQ * 4);
+    orbhip_local_point *dp = (orbhip_local_point *)P.out((size_t)capQ * sizeof(orbhip_local_point));
+    int32_t *dm = n ? (int32_t *)P.out((size_t)n * 4) : nullptr;
+    uint8_t *dskip = Q.d_skip;
+    if ((rc = P.upload())) return rc;
+    uint32_t *marks = K->marks.as<uint32_t>();
+    launch_mark_add(c->stream, dseen, nseen, M->maxPoints, marks);
+    launch_collect(c->stream, K->rows.as<void>(), K->rowHigh, K->stride, Q.d_rowIdx, Q.d_off, nkf, Q.total, M->flags.as<uint32_t>(),
+                   M->maxPoints, marks, K->first.as<uint32_t>(), Q.d_cand, Q.d_blockCnt, capQ, dslots, dskip, dc);
+    launch_mark_clear(c->stream, dseen, nseen, M->maxPoints, marks);
+    HIPCHK(c, hipGetLastError());
+    // the list stays where the union left it: the frustum kernel and the window search read slots, skip bytes and the count there
+    if ((rc = local_points_enqueue(c, M, n ? S.d_kps : nullptr, S.d_desc, S.d_cnt, n, 1, dur, docc, S.minX, S.minY, S.invW, S.invH,
+                                   S.d_cellOff, S.d_cellIdx, dcam, dslots, dskip, dc, capQ, nnratio, dp, dc + 1, dm, dc + 2, false)))
+        return rc;
+    if ((rc = P.download(dc))) return rc;   // counts | slots | records | matches: one copy back, one synchronisation
+    const int32_t *hc = (const int32_t *)P.host(dc);
+    const int32_t *hs = (const int32_t *)P.host(dslots);
+    const int got = hc[0];
+    *nlocal = got;
+    if (got > cap) {
+        if (n_to_match) *n_to_match = 0;
+        for (int i = 0; i < capQ; i++) local_keys_out[i] = (hs[i] >= 0 && hs[i] < M->maxPoints) ? M->slotKey[hs[i]] : 0;
+        return fail(c, ORBHIP_E_CAPACITY, "orbhip_track_local_points: more local points than cap (*nlocal has the number)");
+    }
+    for (int i = 0; i < got; i++) local_keys_out[i] = (hs[i] >= 0 && hs[i] < M->maxPoints) ? M->slotKey[hs[i]] : 0;
+    memcpy(points, P.host(dp), (size_t)got * sizeof(orbhip_local_point));
+    if (n) memcpy(match, P.host(dm), (size_t)n * 4);
     if (n_to_match) *n_to_match = hc[1];
     if (nmatches) *nmatches = n ? hc[2] : 0;
     return ORBHIP_OK;

@@ -525,6 +525,16 @@ void launch_map_flags(hipStream_t s, const int32_t *slot, const uint32_t *flags,
 void launch_local_frustum(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
                           const orbhip_local_camera *cams, const int32_t *slots, const uint8_t *skip, const int32_t *nq, int capQ,
                           int B, orbhip_local_point *points, orbhip_proj_query *queries, int32_t *nToMatch);
+// k_localcollect.hip
+void launch_mark_add(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
+void launch_mark_clear(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
+void launch_kf_set(hipStream_t s, const int64_t *at, const void *val, int m, int64_t total, void *rows);
+void launch_vote_rows(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint32_t *mflags, int maxPoints,
+                      const uint32_t *marks, int capOut, int32_t *nout, int32_t *pairs);
+int collect_blocks(uint32_t P);
+void launch_collect(hipStream_t s, const void *rows, int nrows, int stride, const int32_t *rowIdx, const uint32_t *off, int nkf,
+                    uint32_t P, const uint32_t *mflags, int maxPoints, const uint32_t *marks, uint32_t *first, int32_t *cand,
+                    int32_t *blockCnt, int capOut, int32_t *slots, uint8_t *skip, int32_t *nlocal);
 void launch_distinctive(hipStream_t s, const uint8_t *desc, const int32_t *off, int P, int32_t *best, int32_t *bestMedian);
 void launch_tri_match(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const uint8_t *skip1, const float *ur1,
                       const int32_t *off1, const int32_t *idx1, const orbhip_keypoint *kps2, const uint8_t *desc2,

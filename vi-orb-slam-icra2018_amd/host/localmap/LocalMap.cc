@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstring>
 
+#include "LocalMapDetail.h"
 #include "hiperror.h"
 #include "orbhip.h"
 
@@ -15,12 +16,8 @@ namespace ORB_SLAM2
 namespace
 {
 int g_localmap_device = 0;
-
-inline uint64_t key_of(MapPoint *pMP) { return (uint64_t)pMP->mnId + 1; }
-inline uint8_t flags_of(MapPoint *pMP)
-{
-    return (uint8_t)((pMP->Observations() > 0 ? ORBHIP_MP_OBSERVED : 0) | (pMP->isBad() ? ORBHIP_MP_BAD : 0));
-}
+using localmapdetail::flags_of;
+using localmapdetail::key_of;
 }  // namespace
 
 void LocalMapSearch::SetDevice(int device) { g_localmap_device = device; }
@@ -72,8 +69,11 @@ void LocalMapSearch::Put(const std::vector<MapPoint *> &vpMPs)
         memcpy(&desc[32 * i], d.ptr(0), 32);
         fl[i] = flags_of(p);
     }
-    if (orbhip_map_put(mpCtx, (int)n, keys.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), fl.data()) != ORBHIP_OK)
+    if (orbhip_map_put(mpCtx, (int)n, keys.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), fl.data()) != ORBHIP_OK) {
         hipdetail::Fail("LocalMapSearch::Put", orbhip_last_error(mpCtx));
+        return;
+    }
+    for (size_t i = 0; i < n; i++) mPointOf[keys[i]] = vpMPs[i];
 }
 
 void LocalMapSearch::UpdateFlags(MapPoint *pMP)
@@ -90,6 +90,7 @@ void LocalMapSearch::Erase(MapPoint *pMP)
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx) return;
     const uint64_t key = key_of(pMP);
+    mPointOf.erase(key);
     if (orbhip_map_erase(mpCtx, 1, &key) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::Erase", orbhip_last_error(mpCtx));
 }
 
@@ -97,6 +98,7 @@ void LocalMapSearch::Clear()
 {
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx) return;
+    mPointOf.clear();
     if (orbhip_map_clear(mpCtx) != ORBHIP_OK || orbhip_set_drop(mpCtx, 0) != ORBHIP_OK)
         hipdetail::Fail("LocalMapSearch::Clear", orbhip_last_error(mpCtx));
 }
@@ -112,34 +114,10 @@ int LocalMapSearch::SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &v
     if (F.mnScaleLevels < 1 || F.mnScaleLevels > 16 || (int)F.mvScaleFactors.size() < F.mnScaleLevels)
         return hipdetail::Fail("LocalMapSearch::SearchLocalPoints", "the frame has no scale pyramid (mnScaleLevels, mvScaleFactors)"), 0;
 
-    // the frame as a resident set with a grid, under Frame::mnId + 1: uploaded the first time the frame is searched
-    const uint64_t frameKey = n > 0 ? (uint64_t)F.mnId + 1 : 0;
-    if (n > 0 && !orbhip_set_has(mpCtx, frameKey, n)) {
-        std::vector<uint8_t> d((size_t)n * 32);
-        for (int i = 0; i < n; i++) memcpy(&d[(size_t)i * 32], F.mDescriptors.ptr(i), 32);
-        if (orbhip_set_put(mpCtx, frameKey, reinterpret_cast<const orbhip_keypoint *>(F.mvKeysUn.data()), d.data(), n, NULL, NULL, NULL,
-                           0, Frame::mnMinX, Frame::mnMinY, Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv) != ORBHIP_OK)
-            return hipdetail::Fail("LocalMapSearch::SearchLocalPoints (orbhip_set_put)", orbhip_last_error(mpCtx)), 0;
-    }
-
+    uint64_t frameKey = 0;
+    if (!localmapdetail::put_frame(mpCtx, F, &frameKey)) return hipdetail::Fail("LocalMapSearch::SearchLocalPoints (orbhip_set_put)", orbhip_last_error(mpCtx)), 0;
     orbhip_local_camera cam;
-    memset(&cam, 0, sizeof cam);
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) cam.Rcw[3 * r + c] = F.mTcw.at<float>(r, c);    // mRcw, mtcw (ref: Frame::UpdatePoseMatrices)
-        cam.tcw[r] = F.mTcw.at<float>(r, 3);
-    }
-    for (int r = 0; r < 3; r++) {   // mOw = -mRcw.t()*mtcw: one gemm with alpha = -1, summed in double, one rounding
-        double s = 0;
-        for (int k = 0; k < 3; k++) s += (double)cam.Rcw[3 * k + r] * (double)cam.tcw[k];
-        cam.Ow[r] = (float)(-1.0 * s);
-    }
-    cam.fx = Frame::fx, cam.fy = Frame::fy, cam.cx = Frame::cx, cam.cy = Frame::cy, cam.mbf = F.mbf;
-    cam.min_x = Frame::mnMinX, cam.max_x = Frame::mnMaxX, cam.min_y = Frame::mnMinY, cam.max_y = Frame::mnMaxY;
-    for (int l = 0; l < F.mnScaleLevels; l++) cam.scale_factors[l] = F.mvScaleFactors[l];
-    cam.log_scale_factor = F.mfLogScaleFactor;
-    cam.nlevels = F.mnScaleLevels;
-    cam.viewing_cos_limit = viewingCosLimit;
-    cam.th = th;
+    localmapdetail::fill_camera(F, th, viewingCosLimit, &cam);
 
     std::vector<uint64_t> keys(nq);
     std::vector<uint8_t> skip(nq), occupied(n > 0 ? n : 1, 0);
@@ -156,19 +134,7 @@ int LocalMapSearch::SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &v
                                               occupied.data(), &cam, keys.data(), skip.data(), nq, 0.8f, pts.data(), &ntm,
                                               match.data(), &found);   // 0.8: the matcher Tracking constructs here
     if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::SearchLocalPoints", orbhip_last_error(mpCtx)), 0;
-    for (int k = 0; k < nq; k++) {
-        MapPoint *p = vpLocalMapPoints[k];
-        if (skip[k] || p->isBad()) continue;                   // ref: :2342-2345 -- the loop does not touch these
-        p->mbTrackInView = pts[k].in_view != 0;                // ref: src/Frame.cc:615
-        if (!pts[k].in_view) continue;
-        p->mTrackProjX = pts[k].u;                             // ref: :661-666
-        p->mTrackProjXR = pts[k].proj_xr;
-        p->mTrackProjY = pts[k].v;
-        p->mnTrackScaleLevel = pts[k].level;
-        p->mTrackViewCos = pts[k].view_cos;
-    }
-    for (int i = 0; i < n; i++)
-        if (match[i] >= 0 && match[i] < nq) F.mvpMapPoints[i] = vpLocalMapPoints[match[i]];   // ref: src/ORBmatcher.cc:123
+    localmapdetail::write_back(F, vpLocalMapPoints, skip, pts, match);
     if (nToMatch) *nToMatch = ntm;
     return found;
 }

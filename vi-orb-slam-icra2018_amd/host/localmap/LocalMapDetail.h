@@ -1,0 +1,92 @@
+// LocalMapDetail.h -- what LocalMap.cc and LocalMapCollect.cc share: keys and flags of a MapPoint, the frame as a resident
+// set, the camera block of a search and the write-back of its results (ref: src/Tracking.cc:2336-2364, src/Frame.cc:613-669,
+// src/ORBmatcher.cc:45-129).
+#ifndef ORBHIP_LOCALMAP_DETAIL_H
+#define ORBHIP_LOCALMAP_DETAIL_H
+
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "LocalMap.h"
+#include "orbhip.h"
+
+namespace ORB_SLAM2
+{
+namespace localmapdetail
+{
+inline uint64_t key_of(MapPoint *pMP) { return (uint64_t)pMP->mnId + 1; }
+inline uint64_t key_of(KeyFrame *pKF) { return (uint64_t)pKF->mnId + 1; }
+inline uint8_t flags_of(MapPoint *pMP)
+{
+    return (uint8_t)((pMP->Observations() > 0 ? ORBHIP_MP_OBSERVED : 0) | (pMP->isBad() ? ORBHIP_MP_BAD : 0));
+}
+
+// the frame as a resident set with a grid, under Frame::mnId + 1 (0 for a frame without features): uploaded the first time the
+// frame is searched
+inline bool put_frame(orbhip_ctx *ctx, Frame &F, uint64_t *frameKey)
+{
+    const int n = F.N;
+    *frameKey = n > 0 ? (uint64_t)F.mnId + 1 : 0;
+    if (n > 0 && !orbhip_set_has(ctx, *frameKey, n)) {
+        std::vector<uint8_t> d((size_t)n * 32);
+        for (int i = 0; i < n; i++) memcpy(&d[(size_t)i * 32], F.mDescriptors.ptr(i), 32);
+        if (orbhip_set_put(ctx, *frameKey, reinterpret_cast<const orbhip_keypoint *>(F.mvKeysUn.data()), d.data(), n, NULL, NULL, NULL,
+                           0, Frame::mnMinX, Frame::mnMinY, Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv) != ORBHIP_OK)
+            return false;
+    }
+    return true;
+}
+
+inline void fill_camera(Frame &F, float th, float viewingCosLimit, orbhip_local_camera *out)
+{
+    orbhip_local_camera &cam = *out;
+    memset(&cam, 0, sizeof cam);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) cam.Rcw[3 * r + c] = F.mTcw.at<float>(r, c);    // mRcw, mtcw (ref: Frame::UpdatePoseMatrices)
+        cam.tcw[r] = F.mTcw.at<float>(r, 3);
+    }
+    for (int r = 0; r < 3; r++) {   // mOw = -mRcw.t()*mtcw: one gemm with alpha = -1, summed in double, one rounding
+        double s = 0;
+        for (int k = 0; k < 3; k++) s += (double)cam.Rcw[3 * k + r] * (double)cam.tcw[k];
+        cam.Ow[r] = (float)(-1.0 * s);
+    }
+    cam.fx = Frame::fx, cam.fy = Frame::fy, cam.cx = Frame::cx, cam.cy = Frame::cy, cam.mbf = F.mbf;
+    cam.min_x = Frame::mnMinX, cam.max_x = Frame::mnMaxX, cam.min_y = Frame::mnMinY, cam.max_y = Frame::mnMaxY;
+    for (int l = 0; l < F.mnScaleLevels; l++) cam.scale_factors[l] = F.mvScaleFactors[l];
+    cam.log_scale_factor = F.mfLogScaleFactor;
+    cam.nlevels = F.mnScaleLevels;
+    cam.viewing_cos_limit = viewingCosLimit;
+    cam.th = th;
+}
+
+// occupied[i] = the feature holds a point with observations (ref: src/ORBmatcher.cc:87-89)
+inline void fill_occupied(Frame &F, std::vector<uint8_t> &occupied)
+{
+    occupied.assign(F.N > 0 ? F.N : 1, 0);
+    for (int i = 0; i < F.N; i++)
+        if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) occupied[i] = 1;
+}
+
+inline void write_back(Frame &F, const std::vector<MapPoint *> &vpLocalMapPoints, const std::vector<uint8_t> &skip,
+                       const std::vector<orbhip_local_point> &pts, const std::vector<int32_t> &match)
+{
+    const int n = F.N, nq = (int)vpLocalMapPoints.size();
+    for (int k = 0; k < nq; k++) {
+        MapPoint *p = vpLocalMapPoints[k];
+        if (skip[k] || p->isBad()) continue;                   // ref: :2342-2345 -- the loop does not touch these
+        p->mbTrackInView = pts[k].in_view != 0;                // ref: src/Frame.cc:615
+        if (!pts[k].in_view) continue;
+        p->mTrackProjX = pts[k].u;                             // ref: :661-666
+        p->mTrackProjXR = pts[k].proj_xr;
+        p->mTrackProjY = pts[k].v;
+        p->mnTrackScaleLevel = pts[k].level;
+        p->mTrackViewCos = pts[k].view_cos;
+    }
+    for (int i = 0; i < n; i++)
+        if (match[i] >= 0 && match[i] < nq) F.mvpMapPoints[i] = vpLocalMapPoints[match[i]];   // ref: src/ORBmatcher.cc:123
+}
+}  // namespace localmapdetail
+}  // namespace ORB_SLAM2
+
+#endif

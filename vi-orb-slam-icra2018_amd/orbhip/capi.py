@@ -62,6 +62,8 @@ SYMBOLS = [
     "orbhip_map_init", "orbhip_map_clear", "orbhip_map_info", "orbhip_map_put", "orbhip_map_update_flags", "orbhip_map_erase",
     "orbhip_map_slots", "orbhip_local_camera_prepare", "orbhip_debug_predict_scale_table", "orbhip_search_local_points",
     "orbhip_search_local_points_device",
+    "orbhip_map_kf_init", "orbhip_map_kf_clear", "orbhip_map_kf_info", "orbhip_map_kf_put", "orbhip_map_kf_set", "orbhip_map_kf_erase",
+    "orbhip_map_vote", "orbhip_map_collect", "orbhip_track_local_points",
     "orbhip_grey", "orbhip_grey_device", "orbhip_extract_color", "orbhip_rgbd_depth", "orbhip_rgbd_depth_device",
     "orbhip_frame_build_rgbd",
     "orbhip_init_score", "orbhip_init_score_device",
@@ -226,6 +228,15 @@ def load():
     L.orbhip_search_local_points.argtypes = [vp, u64, vp, vp, vp, vp, vp, i32, f32, vp, ip, vp, ip]
     L.orbhip_search_local_points_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp,
                                                     i32, f32, vp, vp, vp, vp]
+    L.orbhip_map_kf_init.argtypes = [vp, i32, i32]
+    L.orbhip_map_kf_clear.argtypes = [vp]
+    L.orbhip_map_kf_info.argtypes = [vp, ip, ip, ip]
+    L.orbhip_map_kf_put.argtypes = [vp, u64, i32, vp]
+    L.orbhip_map_kf_set.argtypes = [vp, u64, i32, vp, vp]
+    L.orbhip_map_kf_erase.argtypes = [vp, u64]
+    L.orbhip_map_vote.argtypes = [vp, i32, vp, vp, vp, i32, ip]
+    L.orbhip_map_collect.argtypes = [vp, i32, vp, vp, i32, ip]
+    L.orbhip_track_local_points.argtypes = [vp, u64, vp, vp, vp, i32, vp, i32, vp, f32, vp, i32, ip, vp, ip, vp, ip]
     L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
     L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]

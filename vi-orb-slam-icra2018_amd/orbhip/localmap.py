@@ -43,10 +43,12 @@ def predict_scale_table(log_scale_factor, nlevels):
 class LocalMap:
     """The map points of one context (an ORBextractor, or anything with .handle): put / update_flags / erase / clear / search."""
 
-    def __init__(self, ctx, max_points):
+    def __init__(self, ctx, max_points, max_kfs=0, max_row=0):
         self._L = capi.load()
         self._ctx = ctx
         check(self._L.orbhip_map_init(ctx.handle, max_points), ctx.handle, "orbhip_map_init")
+        if max_kfs:
+            self.kf_init(max_kfs, max_row)
 
     def info(self):
         live, cap = C.c_int(), C.c_int()
@@ -101,3 +103,71 @@ class LocalMap:
                                                  nnratio, _p(pts), C.byref(ntm), _p(match), C.byref(nm)), self._ctx.handle,
               "orbhip_search_local_points")
         return pts[:len(keys)].copy(), ntm.value, nm.value, match[:n].copy()
+
+    # ---- the key-frame -> map-point table, the vote and the ordered union ----
+    def kf_init(self, max_kfs, max_row):
+        check(self._L.orbhip_map_kf_init(self._ctx.handle, max_kfs, max_row), self._ctx.handle, "orbhip_map_kf_init")
+
+    def kf_clear(self):
+        check(self._L.orbhip_map_kf_clear(self._ctx.handle), self._ctx.handle, "orbhip_map_kf_clear")
+
+    def kf_info(self):
+        """(live rows, max_kfs, max_row)"""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        check(self._L.orbhip_map_kf_info(self._ctx.handle, C.byref(a), C.byref(b), C.byref(c)), self._ctx.handle, "orbhip_map_kf_info")
+        return a.value, b.value, c.value
+
+    def kf_put(self, kf_key, point_keys):
+        pk = np.ascontiguousarray(point_keys, np.uint64)
+        check(self._L.orbhip_map_kf_put(self._ctx.handle, kf_key, len(pk), _p(pk)), self._ctx.handle, "orbhip_map_kf_put")
+
+    def kf_set(self, kf_key, idx, point_keys):
+        idx, pk = np.ascontiguousarray(idx, np.int32).ravel(), np.ascontiguousarray(point_keys, np.uint64).ravel()
+        assert len(idx) == len(pk)
+        check(self._L.orbhip_map_kf_set(self._ctx.handle, kf_key, len(idx), _p(idx), _p(pk)), self._ctx.handle, "orbhip_map_kf_set")
+
+    def kf_erase(self, kf_key):
+        check(self._L.orbhip_map_kf_erase(self._ctx.handle, kf_key), self._ctx.handle, "orbhip_map_kf_erase")
+
+    def vote(self, frame_point_keys, cap=None):
+        """(kf_keys ascending, counts) of the key frames that hold at least one of the frame's points."""
+        fk = np.ascontiguousarray(frame_point_keys, np.uint64)
+        cap = self.kf_info()[1] if cap is None else cap
+        keys, counts, n = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.int32), C.c_int()
+        try:
+            check(self._L.orbhip_map_vote(self._ctx.handle, len(fk), _p(fk), _p(keys), _p(counts), cap, C.byref(n)), self._ctx.handle,
+                  "orbhip_map_vote")
+        except capi.OrbHipError as e:     # too little room: the first cap entries are filled, .total has the number
+            e.partial, e.total = (keys[:cap].copy(), counts[:cap].copy()), n.value
+            raise
+        return keys[:n.value].copy(), counts[:n.value].copy()
+
+    def collect(self, kf_keys, cap):
+        """The keys of mvpLocalMapPoints for mvpLocalKeyFrames = kf_keys, in the reference's order."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        out, n = np.zeros(max(cap, 1), np.uint64), C.c_int()
+        try:
+            check(self._L.orbhip_map_collect(self._ctx.handle, len(kk), _p(kk), _p(out), cap, C.byref(n)), self._ctx.handle,
+                  "orbhip_map_collect")
+        except capi.OrbHipError as e:
+            e.partial, e.total = out[:cap].copy(), n.value
+            raise
+        return out[:n.value].copy()
+
+    def track(self, frame_key, n, cam, kf_keys, seen_keys, cap, nnratio=0.8, u_right=None, occupied=None):
+        """collect + search in one call.  Returns (local_keys, points, n_to_match, nmatches, match)."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        kk, sk = np.ascontiguousarray(kf_keys, np.uint64), np.ascontiguousarray(seen_keys, np.uint64)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, f32)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        keys, pts = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), POINT_DTYPE)
+        match = np.empty(max(n, 1), np.int32)
+        nl, ntm, nm = C.c_int(), C.c_int(), C.c_int()
+        try:
+            check(self._L.orbhip_track_local_points(self._ctx.handle, frame_key, _p(ur), _p(occ), _p(cam), len(kk), _p(kk), len(sk), _p(sk),
+                                                    nnratio, _p(keys), cap, C.byref(nl), _p(pts), C.byref(ntm), _p(match), C.byref(nm)),
+                  self._ctx.handle, "orbhip_track_local_points")
+        except capi.OrbHipError as e:
+            e.partial, e.total = keys[:cap].copy(), nl.value
+            raise
+        return keys[:nl.value].copy(), pts[:nl.value].copy(), ntm.value, nm.value, match[:n].copy()

@@ -257,7 +257,9 @@ int orbhip_vocab_info(const orbhip_ctx *ctx, int *k, int *L, int *scoring, int *
                       int *nwords);
 /* Replaces the per-feature ORBVocabulary::transform (TemplatedVocabulary.h:1443-1485) as used by
  * Frame::ComputeBoW / KeyFrame::ComputeBoW (src/Frame.cc:739-746, src/KeyFrame.cc:392-400): word id and
- * weight of the leaf reached, node id at level L - levelsup (0 if that level is <= 0).  The caller builds
+ * weight of the leaf reached, node id at level L - levelsup; node id 0 if that level is <= 0 and -- canonical, the
+ * reference leaves the value unset -- if the leaf lies above level L - levelsup (a built vocabulary has leaves at every
+ * depth).  The caller builds
  * BowVector (sum of weights per word, normalised) and FeatureVector (indices per node, weight > 0 only)
  * from these arrays. */
 int orbhip_vocab_transform(orbhip_ctx *ctx, const uint8_t *desc, int n, int levelsup, int32_t *word_id,

@@ -497,6 +497,28 @@ int orbhip_search_by_bow_sets(orbhip_ctx *ctx, uint64_t key1, const uint8_t *val
 /* orbhip_window_best (above) into a resident set (with a grid): the projected points travel, the key frame does not. */
 int orbhip_window_best_set(orbhip_ctx *ctx, uint64_t key, const float *u_right, const float *inv_level_sigma2, int nlevels,
                            const orbhip_proj_query *queries, const uint8_t *qdesc, int nq, int32_t *best_idx, int32_t *best_dist);
+/* orbhip_search_for_triangulation (above) of key frame 1 against K neighbours in ONE call, every key frame a resident set
+ * (LocalMapping::CreateNewMapPoints calls SearchForTriangulation once per neighbour of the new key frame, 20 of them in the
+ * monocular case: ref src/LocalMapping.cc:2226-2298).  Row k of matches12 ([K][n1], n1 = the features of set key1) and
+ * nmatches[k] equal what orbhip_search_for_triangulation returns for neighbour k on the sets' data.
+ *   skip1[n1], u_right1[n1]   of key frame 1, shared by all neighbours (u_right1 NULL: monocular)
+ *   nb[K]                     per neighbour: its set, F12 (row-major) and the epipole in its image; a key may appear several
+ *                             times, and key2 == key1 is allowed
+ *   skip2, u_right2           the K per-neighbour arrays one after the other in neighbour order, each as long as its set
+ *                             (orbhip_set_info); u_right2 NULL: monocular
+ * Only these, the shared nodes and the K parameter records travel.  K == 0 returns ORBHIP_OK and writes nothing.
+ * ORBHIP_E_ARG, with nothing written: a key that is not resident, K < 0, more distinct keys than the set limit in force
+ * (orbhip_set_limit), nlevels2 outside 1..64, a set of more than 65535 features on side 2, a side-2 set with an octave
+ * outside [0, nlevels2). */
+typedef struct orbhip_tri_neighbour {
+    uint64_t key2;      /* resident set of pKF2 */
+    float F12[9];       /* row-major, as for orbhip_search_for_triangulation */
+    float ex, ey;       /* epipole in image 2 */
+} orbhip_tri_neighbour;
+int orbhip_search_for_triangulation_sets(orbhip_ctx *ctx, uint64_t key1, const uint8_t *skip1, const float *u_right1,
+                                         const orbhip_tri_neighbour *nb, int K, const uint8_t *skip2, const float *u_right2,
+                                         const float *scale_factors2, const float *level_sigma2_2, int nlevels2,
+                                         int only_stereo, int check_ori, int32_t *matches12 /* [K][n1] */, int32_t *nmatches /* [K] */);
 
 /* ---- the Frame constructor's device work as one launch (new) ----
  * Frame::Frame (ref: src/Frame.cc:518-572) runs ExtractORB (:591-597), UndistortKeyPoints (:748-778) and AssignFeaturesToGrid
@@ -547,7 +569,9 @@ int orbhip_debug_roundtrip(orbhip_ctx *ctx, int mode, int iters, double *us_per_
  * checks the bit).  Bits: 0 k_fast_fix, 1 k_fast (generic grid), 2 k_resize_fit, 3 k_resize<32> / <8>, 4 k_pyramid_chain,
  * 5 k_quadtree (tables in LDS), 6 k_quadtree (tables and candidates in LDS, a frame or two), 7 k_quadtree (tables in global
  * memory), 8 k_bow_lane, 9 k_bow_seq (descriptors in LDS), 10 k_bow_seq (descriptors in global memory), 11 k_fast_fix on the
- * tall-cell instance.  Returns the mask; reset != 0 clears it. */
+ * tall-cell instance, 12 k_describe, 13 k_describe_blur, 14 k_blur, 15 k_tri_match_sets with a node of at most 128 side-2
+ * features (held in registers), 16 k_tri_match_sets with a node of more than 128 (strided).  Returns the mask; reset != 0
+ * clears it. */
 unsigned orbhip_debug_path_mask(int reset);
 
 /* ---- multi-GPU (one process per GPU) ----

@@ -73,6 +73,8 @@ int orb_match_scratch(orbhip_ctx *c, size_t bytes);
 void orb_three_maxima(const std::vector<int> *histo, int L, int &ind1, int &ind2, int &ind3);
 int orb_bow_rotation_check(const int32_t *pairs, int npairs, const int32_t *off1, const int32_t *idx1, const float *angle1,
                            const float *angle2, int check_ori, int32_t *match12, int32_t *match21);
+int orb_tri_rotation_check(const float *angle1, size_t stride1, const float *angle2, size_t stride2, int n1, int check_ori,
+                           int32_t *matches12);
 // api_sets.hip
 void orb_sets_release(orbhip_ctx *c);
 // api_kfdb.hip

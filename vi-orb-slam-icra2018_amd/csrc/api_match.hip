@@ -462,6 +462,42 @@ extern "C" int orbhip_distinctive_descriptors(orbhip_ctx *c, const uint8_t *desc
     return ORBHIP_OK;
 }
 
+// Rotation consistency of SearchForTriangulation (ref: src/ORBmatcher.cc:745-755, :775-794) over one row of matches: the
+// matches outside the three fullest of 30 angle-difference bins are taken back.  The angles are read `stride` bytes apart (a
+// keypoint array, or the float array a resident set mirrors).  Returns the number of matches left.
+int orb_tri_rotation_check(const float *angle1, size_t stride1, const float *angle2, size_t stride2, int n1, int check_ori,
+                           int32_t *matches12)
+{
+    auto at = [](const float *a, size_t stride, int i) { return *(const float *)((const char *)a + stride * (size_t)i); };
+    int nm = 0;
+    std::vector<int> hist[30];
+    const float factor = 1.0f / 30;
+    for (int i1 = 0; i1 < n1; i1++) {
+        const int i2 = matches12[i1];
+        if (i2 < 0) continue;
+        nm++;
+        if (check_ori) {
+            float rot = at(angle1, stride1, i1) - at(angle2, stride2, i2);
+            if (rot < 0.0) rot += 360.0f;
+            int bin = (int)roundf(rot * factor);
+            if (bin == 30) bin = 0;
+            if (bin >= 0 && bin < 30) hist[bin].push_back(i1);
+        }
+    }
+    if (check_ori) {
+        int a, b, d;
+        orb_three_maxima(hist, 30, a, b, d);
+        for (int i = 0; i < 30; i++) {
+            if (i == a || i == b || i == d) continue;
+            for (int i1 : hist[i]) {
+                matches12[i1] = -1;
+                nm--;
+            }
+        }
+    }
+    return nm;
+}
+
 extern "C" int orbhip_search_for_triangulation(orbhip_ctx *c, const orbhip_keypoint *kps1, const uint8_t *desc1, int n1,
                                                const uint8_t *skip1, const float *u_right1, const int32_t *node1,
                                                const int32_t *off1, const int32_t *idx1, int ng1,
@@ -521,34 +557,8 @@ extern "C" int orbhip_search_for_triangulation(orbhip_ctx *c, const orbhip_keypo
     HIPCHK(c, hipGetLastError());
     if ((rc = P.download(dm))) return rc;
     memcpy(matches12, P.host(dm), (size_t)n1 * 4);
-    // rotation consistency (ref: :745-755, :775-794)
-    int nm = 0;
-    std::vector<int> hist[30];
-    const float factor = 1.0f / 30;
-    for (int i1 = 0; i1 < n1; i1++) {
-        const int i2 = matches12[i1];
-        if (i2 < 0) continue;
-        nm++;
-        if (check_ori) {
-            float rot = kps1[i1].angle - kps2[i2].angle;
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int)roundf(rot * factor);
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30) hist[bin].push_back(i1);
-        }
-    }
-    if (check_ori) {
-        int a, b, d;
-        orb_three_maxima(hist, 30, a, b, d);
-        for (int i = 0; i < 30; i++) {
-            if (i == a || i == b || i == d) continue;
-            for (int i1 : hist[i]) {
-                matches12[i1] = -1;
-                nm--;
-            }
-        }
-    }
-    *nmatches = nm;
+    *nmatches = orb_tri_rotation_check(&kps1[0].angle, sizeof(orbhip_keypoint), &kps2[0].angle, sizeof(orbhip_keypoint), n1,
+                                       check_ori, matches12);
     return ORBHIP_OK;
 }
 

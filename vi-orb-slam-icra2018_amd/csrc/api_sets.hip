@@ -22,6 +22,7 @@ struct OrbSetMem {
 struct OrbSet {
     uint64_t key = 0, fingerprint = 0;
     int n = 0, ng = 0;
+    int octMin = 0, octMax = 0;        // range of the keypoints' octaves (a search that indexes a per-level table checks it)
     bool grid = false;
     float minX = 0, minY = 0, invW = 0, invH = 0;
     OrbSetMem mem;
@@ -239,6 +240,18 @@ static hipError_t csr_upload(orbhip_ctx *c, OrbSet *s, const int32_t *node, cons
                           hipMemcpyHostToDevice, c->stream);
 }
 
+// host mirrors of a new set's keypoints: the angles (rotation histograms) and the octave range
+static void mirror_keypoints(OrbSet *s, const orbhip_keypoint *kps, int n)
+{
+    s->angle.resize(n);
+    s->octMin = s->octMax = n > 0 ? kps[0].octave : 0;
+    for (int i = 0; i < n; i++) {
+        s->angle[i] = kps[i].angle;
+        s->octMin = std::min(s->octMin, (int)kps[i].octave);
+        s->octMax = std::max(s->octMax, (int)kps[i].octave);
+    }
+}
+
 extern "C" int orbhip_set_put(orbhip_ctx *c, uint64_t key, const orbhip_keypoint *kps, const uint8_t *desc, int n,
                               const int32_t *node, const int32_t *off, const int32_t *idx, int ng, float min_x, float min_y,
                               float inv_w, float inv_h)
@@ -277,8 +290,7 @@ extern "C" int orbhip_set_put(orbhip_ctx *c, uint64_t key, const orbhip_keypoint
         set_retire(T, s);
         return fail(c, ORBHIP_E_HIP, std::string("orbhip_set_put: ") + hipGetErrorString(e));
     }
-    s->angle.resize(n);
-    for (int i = 0; i < n; i++) s->angle[i] = kps[i].angle;
+    mirror_keypoints(s, kps, n);
     s->stamp = ++T->clock;
     T->sets.push_back(s);
     return ORBHIP_OK;
@@ -338,8 +350,7 @@ extern "C" int orbhip_set_put_from_frame(orbhip_ctx *c, uint64_t key, orbhip_ctx
         set_retire(T, s);
         return fail(c, ORBHIP_E_HIP, std::string("orbhip_set_put_from_frame: ") + hipGetErrorString(e));
     }
-    s->angle.resize(n);
-    for (int i = 0; i < n; i++) s->angle[i] = hkps[i].angle;
+    mirror_keypoints(s, hkps, n);
     s->stamp = ++T->clock;
     T->sets.push_back(s);
     return ORBHIP_OK;
@@ -409,6 +420,105 @@ extern "C" int orbhip_search_by_bow_sets(orbhip_ctx *c, uint64_t key1, const uin
     }
     *nmatches = orb_bow_rotation_check(pairs.data(), npairs, s1->off.data(), s1->idx.data(), s1->angle.data(), s2->angle.data(),
                                        check_ori, match12, match21);
+    return ORBHIP_OK;
+}
+
+// SearchForTriangulation of one key frame against K neighbours, all of them resident sets (ref: src/ORBmatcher.cc:657-827, called
+// per neighbour by LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:2258-2298): one upload -- skip bytes, mvuRight, the
+// shared nodes of every neighbour, one parameter record per neighbour --, one launch over all of it, one synchronisation.  The
+// matches land in page-locked memory; the rotation histogram runs per row on the sets' mirrored angles.  Row k equals what
+// orbhip_search_for_triangulation returns for neighbour k.
+extern "C" int orbhip_search_for_triangulation_sets(orbhip_ctx *c, uint64_t key1, const uint8_t *skip1, const float *u_right1,
+                                                    const orbhip_tri_neighbour *nb, int K, const uint8_t *skip2,
+                                                    const float *u_right2, const float *scale_factors2,
+                                                    const float *level_sigma2_2, int nlevels2, int only_stereo, int check_ori,
+                                                    int32_t *matches12, int32_t *nmatches)
+{
+    const char *who = "orbhip_search_for_triangulation_sets";
+    if (!c || K < 0) return fail(c, ORBHIP_E_ARG, std::string(who) + ": bad argument");
+    if (K == 0) return ORBHIP_OK;
+    if (!skip1 || !nb || !skip2 || !scale_factors2 || !level_sigma2_2 || !matches12 || !nmatches)
+        return fail(c, ORBHIP_E_ARG, std::string(who) + ": bad argument");
+    if (nlevels2 < 1 || nlevels2 > 64) return fail(c, ORBHIP_E_ARG, std::string(who) + ": nlevels2 must be within 1..64");
+    std::vector<uint64_t> keys(1, key1);
+    for (int k = 0; k < K; k++)
+        if (std::find(keys.begin(), keys.end(), nb[k].key2) == keys.end()) keys.push_back(nb[k].key2);
+    if (keys.size() > (size_t)table(c)->limit)
+        return fail(c, ORBHIP_E_ARG, std::string(who) + ": more distinct sets than the set limit in force (orbhip_set_limit)");
+    OrbSet *s1 = find_set(c, key1);
+    std::vector<OrbSet *> s2(K);
+    for (int k = 0; k < K; k++) s2[k] = find_set(c, nb[k].key2);
+    if (!s1 || std::find(s2.begin(), s2.end(), nullptr) != s2.end())
+        return fail(c, ORBHIP_E_ARG, std::string(who) + ": unknown set (orbhip_set_put)");
+    for (int k = 0; k < K; k++) {
+        // (k_tri_match_sets keeps the position inside a node's side-2 list in 16 bits and indexes the per-level tables by octave)
+        if (s2[k]->n > 65535) return fail(c, ORBHIP_E_ARG, std::string(who) + ": more than 65535 features in a set of key frame 2");
+        if (s2[k]->octMin < 0 || s2[k]->octMax >= nlevels2)
+            return fail(c, ORBHIP_E_ARG, std::string(who) + ": octave of key frame 2 out of range");
+    }
+    const int n1 = s1->n;
+    for (size_t i = 0; i < (size_t)K * n1; i++) matches12[i] = -1;
+    for (int k = 0; k < K; k++) nmatches[k] = 0;
+    std::vector<TriPair> pairs;
+    std::vector<TriNeighbourDev> tab(K);
+    bool anyRegister = false, anyStrided = false;
+    size_t total2 = 0;
+    for (int k = 0; k < K; k++) {
+        const OrbSet *t = s2[k];
+        TriNeighbourDev &r = tab[k];
+        r.kps2 = t->d_kps;
+        r.desc2 = t->d_desc;
+        r.off2 = t->d_off;
+        r.idx2 = t->d_idx;
+        r.skipOff = r.urOff = (int)total2;
+        r.row = k;
+        r.pad = 0;
+        for (int i = 0; i < 9; i++) r.P.F[i] = nb[k].F12[i];
+        r.P.ex = nb[k].ex;
+        r.P.ey = nb[k].ey;
+        r.P.only_stereo = only_stereo ? 1 : 0;
+        r.P.th_low = 50;   // TH_LOW
+        total2 += (size_t)t->n;
+        for (int g1 = 0, g2 = 0; g1 < s1->ng && g2 < t->ng;) {     // merge walk over the two FeatureVectors (ref: :690-765)
+            if (s1->node[g1] == t->node[g2]) {
+                const int cnt2 = t->off[g2 + 1] - t->off[g2];
+                if (cnt2 > 0 && s1->off[g1 + 1] > s1->off[g1]) {
+                    (cnt2 <= 128 ? anyRegister : anyStrided) = true;
+                    pairs.push_back({g1, g2, k});
+                }
+                g1++;
+                g2++;
+            } else if (s1->node[g1] < t->node[g2])
+                g1++;
+            else
+                g2++;
+        }
+    }
+    const int npairs = (int)pairs.size();
+    if (npairs == 0) return ORBHIP_OK;
+    HIPCHK(c, orb_enter(c));
+    Packed P(c);
+    int rc;
+    const size_t outBytes = (size_t)K * n1 * 4;
+    if ((rc = P.begin((size_t)n1 * 5 + total2 * 5 + pairs.size() * sizeof(TriPair) + tab.size() * sizeof(TriNeighbourDev) +
+                      (size_t)nlevels2 * 8 + outBytes + 16 * 256)))
+        return rc;
+    const uint8_t *ds1 = (const uint8_t *)P.in(skip1, (size_t)n1), *ds2 = (const uint8_t *)P.in(skip2, total2);
+    const float *du1 = u_right1 ? (const float *)P.in(u_right1, (size_t)n1 * 4) : nullptr;
+    const float *du2 = u_right2 ? (const float *)P.in(u_right2, total2 * 4) : nullptr;
+    const TriPair *dp = (const TriPair *)P.in(pairs.data(), pairs.size() * sizeof(TriPair));
+    const TriNeighbourDev *dt = (const TriNeighbourDev *)P.in(tab.data(), tab.size() * sizeof(TriNeighbourDev));
+    const float *dsf = (const float *)P.in(scale_factors2, (size_t)nlevels2 * 4), *dsg = (const float *)P.in(level_sigma2_2, (size_t)nlevels2 * 4);
+    int32_t *dm = (int32_t *)P.out_host_fill(0xFF, outBytes);   // plain stores, a few hundred per row: written over PCIe, no copy back
+    if ((rc = P.upload())) return rc;
+    launch_tri_match_sets(c->stream, s1->d_kps, s1->d_desc, ds1, du1, s1->d_off, s1->d_idx, n1, dt, ds2, du2, dp, npairs, anyRegister,
+                          anyStrided, dsf, dsg, dm);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    memcpy(matches12, dm, outBytes);
+    for (int k = 0; k < K; k++)
+        nmatches[k] = orb_tri_rotation_check(s1->angle.data(), sizeof(float), s2[k]->angle.data(), sizeof(float), n1, check_ori,
+                                             matches12 + (size_t)k * n1);
     return ORBHIP_OK;
 }
 

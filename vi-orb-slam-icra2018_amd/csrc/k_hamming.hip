@@ -894,30 +894,20 @@ void launch_bow_match(hipStream_t s, const uint8_t *desc1, const uint8_t *valid1
 // distance, the LAST one in the node's list (":719 dist>bestDist continue").  This fork never marks a side-2 feature as
 // taken, so the side-1 features are independent of each other.  Float expressions in the reference's order, no
 // contraction; the final comparison is in double as in the reference (3.84 is a double literal).
-struct TriParams {
-    float F[9];
-    float ex, ey;
-    int only_stereo, th_low;
-};
+// (TriParams: orbhip_internal.h)
 
-__global__ __launch_bounds__(256) void k_tri_match(const orbhip_keypoint *__restrict__ kps1,
-                                                   const uint8_t *__restrict__ desc1, const uint8_t *__restrict__ skip1,
-                                                   const float *__restrict__ ur1, const int32_t *__restrict__ off1,
-                                                   const int32_t *__restrict__ idx1,
-                                                   const orbhip_keypoint *__restrict__ kps2,
-                                                   const uint8_t *__restrict__ desc2, const uint8_t *__restrict__ skip2,
-                                                   const float *__restrict__ ur2, const int32_t *__restrict__ off2,
-                                                   const int32_t *__restrict__ idx2, const int2 *__restrict__ pairs,
-                                                   int npairs, const TriParams P, const float *__restrict__ scale2,
-                                                   const float *__restrict__ sigma2, int32_t *__restrict__ match12)
+// One shared node of one key-frame pair, by one wave: side-1 list entries [a0, a1) of idx1 against the n2 entries of idx2 from b0.
+// The arithmetic of SearchForTriangulation exists here once; k_tri_match and k_tri_match_sets both call it.
+static __device__ __forceinline__ void tri_match_node(const orbhip_keypoint *__restrict__ kps1, const uint8_t *__restrict__ desc1,
+                                                      const uint8_t *__restrict__ skip1, const float *__restrict__ ur1,
+                                                      const int32_t *__restrict__ idx1, const int a0, const int a1,
+                                                      const orbhip_keypoint *__restrict__ kps2, const uint8_t *__restrict__ desc2,
+                                                      const uint8_t *__restrict__ skip2, const float *__restrict__ ur2,
+                                                      const int32_t *__restrict__ idx2, const int b0, const int n2,
+                                                      const TriParams &P, const float *__restrict__ scale2,
+                                                      const float *__restrict__ sigma2, int32_t *__restrict__ match12,
+                                                      const int lane)
 {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int pi = blockIdx.x * 4 + wave;
-    if (pi >= npairs) return;
-    const int2 pr = pairs[pi];
-    const int a0 = off1[pr.x], a1 = off1[pr.x + 1];
-    const int b0 = off2[pr.y], n2 = off2[pr.y + 1] - b0;
-    if (n2 <= 0 || a1 <= a0) return;
     if (n2 <= 128) {
         // The usual node: the side-2 features (descriptor, position, octave thresholds) are loaded ONCE into registers, lane p
         // holding candidates p and p + 64; the side-1 features of the node are loaded 64 at a time, one per lane, and
@@ -1044,6 +1034,62 @@ __global__ __launch_bounds__(256) void k_tri_match(const orbhip_keypoint *__rest
     }
 }
 
+__global__ __launch_bounds__(256) void k_tri_match(const orbhip_keypoint *__restrict__ kps1,
+                                                   const uint8_t *__restrict__ desc1, const uint8_t *__restrict__ skip1,
+                                                   const float *__restrict__ ur1, const int32_t *__restrict__ off1,
+                                                   const int32_t *__restrict__ idx1,
+                                                   const orbhip_keypoint *__restrict__ kps2,
+                                                   const uint8_t *__restrict__ desc2, const uint8_t *__restrict__ skip2,
+                                                   const float *__restrict__ ur2, const int32_t *__restrict__ off2,
+                                                   const int32_t *__restrict__ idx2, const int2 *__restrict__ pairs,
+                                                   int npairs, const TriParams P, const float *__restrict__ scale2,
+                                                   const float *__restrict__ sigma2, int32_t *__restrict__ match12)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * 4 + wave;
+    if (pi >= npairs) return;
+    const int2 pr = pairs[pi];
+    // (a wave handles one pair: said to the compiler, the node offsets and the loop bounds live in SGPRs -- 48 VGPRs instead of 67)
+    const int g1 = __builtin_amdgcn_readfirstlane(pr.x), g2 = __builtin_amdgcn_readfirstlane(pr.y);
+    const int a0 = off1[g1], a1 = off1[g1 + 1];
+    const int b0 = off2[g2], n2 = off2[g2 + 1] - b0;
+    if (n2 <= 0 || a1 <= a0) return;
+    tri_match_node(kps1, desc1, skip1, ur1, idx1, a0, a1, kps2, desc2, skip2, ur2, idx2, b0, n2, P, scale2, sigma2, match12, lane);
+}
+
+// SearchForTriangulation of key frame 1 against K neighbours, every key frame a resident set (api_sets.hip): the grid runs over
+// the shared nodes of ALL neighbours, one wave per {side-1 node, side-2 node, neighbour}.  What differs from neighbour to
+// neighbour -- the side-2 set's device pointers, where its skip bytes and mvuRight start in the concatenated per-call arrays,
+// F12, the epipole, the row of the output -- sits in a table in device memory (20 neighbours do not fit kernel arguments).
+// The neighbour index is the same for a whole wave; readfirstlane tells the compiler so, and the record comes in through
+// scalar loads: the node body has the registers it has in k_tri_match.
+// (TriNeighbourDev, TriPair: orbhip_internal.h)
+__global__ __launch_bounds__(256) void k_tri_match_sets(const orbhip_keypoint *__restrict__ kps1,
+                                                        const uint8_t *__restrict__ desc1, const uint8_t *__restrict__ skip1,
+                                                        const float *__restrict__ ur1, const int32_t *__restrict__ off1,
+                                                        const int32_t *__restrict__ idx1, const int n1,
+                                                        const TriNeighbourDev *__restrict__ nbs,
+                                                        const uint8_t *__restrict__ skip2cat, const float *__restrict__ ur2cat,
+                                                        const TriPair *__restrict__ pairs, const int npairs,
+                                                        const float *__restrict__ scale2, const float *__restrict__ sigma2,
+                                                        int32_t *__restrict__ match12)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pi = blockIdx.x * 4 + wave;
+    if (pi >= npairs) return;
+    const TriPair pr = pairs[pi];
+    const int k = __builtin_amdgcn_readfirstlane(pr.k);
+    const int g1 = __builtin_amdgcn_readfirstlane(pr.g1), g2 = __builtin_amdgcn_readfirstlane(pr.g2);
+    const TriNeighbourDev *nb = nbs + k;
+    const TriParams P = nb->P;
+    const int32_t *off2 = nb->off2;
+    const int a0 = off1[g1], a1 = off1[g1 + 1];
+    const int b0 = off2[g2], n2 = off2[g2 + 1] - b0;
+    if (n2 <= 0 || a1 <= a0) return;
+    tri_match_node(kps1, desc1, skip1, ur1, idx1, a0, a1, nb->kps2, nb->desc2, skip2cat + nb->skipOff,
+                   ur2cat ? ur2cat + nb->urOff : nullptr, nb->idx2, b0, n2, P, scale2, sigma2, match12 + (size_t)nb->row * n1, lane);
+}
+
 void launch_tri_match(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const uint8_t *skip1, const float *ur1,
                       const int32_t *off1, const int32_t *idx1, const orbhip_keypoint *kps2, const uint8_t *desc2,
                       const uint8_t *skip2, const float *ur2, const int32_t *off2, const int32_t *idx2, const int32_t *pairs,
@@ -1059,6 +1105,17 @@ void launch_tri_match(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t 
     P.th_low = th_low;
     hipLaunchKernelGGL(k_tri_match, dim3((npairs + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, kps1, desc1, skip1, ur1, off1, idx1, kps2,
                        desc2, skip2, ur2, off2, idx2, reinterpret_cast<const int2 *>(pairs), npairs, P, scale2, sigma2, match12);
+}
+
+void launch_tri_match_sets(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const uint8_t *skip1, const float *ur1,
+                           const int32_t *off1, const int32_t *idx1, int n1, const TriNeighbourDev *nbs, const uint8_t *skip2cat,
+                           const float *ur2cat, const TriPair *pairs, int npairs, bool anyRegister, bool anyStrided,
+                           const float *scale2, const float *sigma2, int32_t *match12)
+{
+    if (npairs <= 0) return;
+    orb_path((anyRegister ? ORB_PATH_TRI_SETS_REG : 0u) | (anyStrided ? ORB_PATH_TRI_SETS_STRIDED : 0u));
+    hipLaunchKernelGGL(k_tri_match_sets, dim3((npairs + 3) / 4, 1, 1), dim3(256, 1, 1), 0, s, kps1, desc1, skip1, ur1, off1, idx1, n1,
+                       nbs, skip2cat, ur2cat, pairs, npairs, scale2, sigma2, match12);
 }
 
 // ---- MapPoint::ComputeDistinctiveDescriptors (ref: src/MapPoint.cc:283-349) for many points at once ----------------

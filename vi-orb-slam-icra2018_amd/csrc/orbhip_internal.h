@@ -48,7 +48,8 @@ static inline int orb_env_int(const char *name, int dflt)
 enum OrbPath : unsigned {
     ORB_PATH_FAST_FIX = 1u << 0, ORB_PATH_FAST_GENERIC = 1u << 1, ORB_PATH_RESIZE_FIT = 1u << 2, ORB_PATH_RESIZE_TILES = 1u << 3,
     ORB_PATH_PYRAMID_CHAIN = 1u << 4, ORB_PATH_QT_LDS = 1u << 5, ORB_PATH_QT_LDSPTS = 1u << 6, ORB_PATH_QT_GLOBAL = 1u << 7,
-    ORB_PATH_BOW_LANE = 1u << 8, ORB_PATH_BOW_SEQ_LDS = 1u << 9, ORB_PATH_BOW_SEQ_GLOBAL = 1u << 10, ORB_PATH_FAST_TALL = 1u << 11, ORB_PATH_DESCRIBE = 1u << 12, ORB_PATH_DESCRIBE_BLUR = 1u << 13, ORB_PATH_BLUR = 1u << 14
+    ORB_PATH_BOW_LANE = 1u << 8, ORB_PATH_BOW_SEQ_LDS = 1u << 9, ORB_PATH_BOW_SEQ_GLOBAL = 1u << 10, ORB_PATH_FAST_TALL = 1u << 11, ORB_PATH_DESCRIBE = 1u << 12, ORB_PATH_DESCRIBE_BLUR = 1u << 13, ORB_PATH_BLUR = 1u << 14,
+    ORB_PATH_TRI_SETS_REG = 1u << 15, ORB_PATH_TRI_SETS_STRIDED = 1u << 16
 };
 extern std::atomic<unsigned> g_orbPathMask;
 static inline void orb_path(unsigned bit) { g_orbPathMask.fetch_or(bit, std::memory_order_relaxed); }
@@ -541,6 +542,29 @@ void launch_tri_match(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t 
                       const uint8_t *skip2, const float *ur2, const int32_t *off2, const int32_t *idx2, const int32_t *pairs,
                       int npairs, const float F12[9], float ex, float ey, int only_stereo, int th_low, const float *scale2,
                       const float *sigma2, int32_t *match12);
+// SearchForTriangulation: what is the same for every node of one key-frame pair
+struct TriParams {
+    float F[9];
+    float ex, ey;
+    int only_stereo, th_low;
+};
+// k_tri_match_sets: one record per neighbour in device memory, one record per shared node
+struct TriNeighbourDev {
+    const orbhip_keypoint *kps2;
+    const uint8_t *desc2;
+    const int32_t *off2, *idx2;
+    int skipOff, urOff;      // first element of this neighbour in the concatenated skip2 / u_right2
+    int row, pad;            // its output row: match12 + row * n1
+    TriParams P;
+};
+struct TriPair {
+    int g1, g2, k;           // node of key frame 1, node of neighbour k
+};
+// (anyRegister / anyStrided: a node of at most / more than 128 side-2 features is among the pairs -- orbhip_debug_path_mask)
+void launch_tri_match_sets(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const uint8_t *skip1, const float *ur1,
+                           const int32_t *off1, const int32_t *idx1, int n1, const TriNeighbourDev *nbs, const uint8_t *skip2cat,
+                           const float *ur2cat, const TriPair *pairs, int npairs, bool anyRegister, bool anyStrided,
+                           const float *scale2, const float *sigma2, int32_t *match12);
 size_t init_scratch_bytes(int B, int cap1, int cap2);
 size_t init_assign_lds(int cap1, int cap2);
 int launch_search_for_initialization(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const int32_t *cnt1,

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <string>
 
+#include "MatcherDetail.h"
 #include "ORBextractor.h"
 #include "hiperror.h"
 #include "orbhip.h"
@@ -46,26 +47,10 @@ struct ThreadCtx {
 };
 thread_local ThreadCtx tls;
 
-struct Csr {
-    vector<int32_t> node, off, idx;
-};
-Csr flatten(const DBoW2::FeatureVector &fv)
-{
-    Csr c;
-    c.off.push_back(0);
-    for (DBoW2::FeatureVector::const_iterator it = fv.begin(); it != fv.end(); ++it) {
-        c.node.push_back((int32_t)it->first);
-        for (size_t k = 0; k < it->second.size(); k++) c.idx.push_back((int32_t)it->second[k]);
-        c.off.push_back((int32_t)c.idx.size());
-    }
-    return c;
-}
-vector<uint8_t> contiguous(const cv::Mat &d)
-{
-    vector<uint8_t> v((size_t)d.rows * 32);
-    for (int i = 0; i < d.rows; i++) memcpy(&v[(size_t)i * 32], d.ptr(i), 32);
-    return v;
-}
+using hipdetail::Csr;
+using hipdetail::affine3;
+using hipdetail::contiguous;
+using hipdetail::flatten;
 
 // Resident feature sets (include/orbhip.h, orbhip_set_*): descriptors, undistorted keypoints, FeatureVector and feature grid of
 // a key frame or frame stay on the device under its id once a matcher of this thread has met it (a set nobody uses any
@@ -82,31 +67,18 @@ bool use_sets()
     static const bool off = getenv("ORBHIP_NO_SETS") && atoi(getenv("ORBHIP_NO_SETS")) != 0;
     return !off;
 }
+// (the identity rule itself: hipdetail::ensure_set, MatcherDetail.h)
 template <class T>
 bool ensure_set(uint64_t key, const T &t, const vector<cv::KeyPoint> &keysUn, float minX, float minY, float invW, float invH,
                 orbhip_ctx *builder)
 {
-    const int n = t.mDescriptors.rows;
-    if (n <= 0 || (int)keysUn.size() != n) return false;
     orbhip_ctx *c = tls.get();
     const int lim = g_set_limit.load();
     if (lim != tls.limit && c) {
         orbhip_set_limit(c, lim);
         tls.limit = lim;
     }
-    const uint64_t fp = orbhip_set_fingerprint_rows(reinterpret_cast<const orbhip_keypoint *>(keysUn.data()), t.mDescriptors.ptr(0),
-                                                    t.mDescriptors.ptr(n - 1), n);
-    int n0 = 0, ng0 = 0;
-    uint64_t fp0 = 0;
-    if (orbhip_set_info(c, key, &n0, &ng0, &fp0) && n0 == n && fp0 == fp && ng0 == (int)t.mFeatVec.size()) return true;
-    const Csr fv = flatten(t.mFeatVec);
-    // the frame its extractor built last is still on the device: block to block, the FeatureVector alone travels
-    if (builder && orbhip_frame_fingerprint(builder) == fp &&
-        orbhip_set_put_from_frame(c, key, builder, fv.node.data(), fv.off.data(), fv.idx.data(), (int)fv.node.size()) == ORBHIP_OK)
-        return true;
-    const vector<uint8_t> d = contiguous(t.mDescriptors);
-    return orbhip_set_put(c, key, reinterpret_cast<const orbhip_keypoint *>(keysUn.data()), d.data(), n, fv.node.data(),
-                          fv.off.data(), fv.idx.data(), (int)fv.node.size(), minX, minY, invW, invH) == ORBHIP_OK;
+    return hipdetail::ensure_set(c, key, t, keysUn, minX, minY, invW, invH, builder);
 }
 bool ensure_set(KeyFrame *pKF)
 {
@@ -255,16 +227,6 @@ int run_projection_search(Frame &F, const vector<orbhip_proj_query> &q, const ve
     return found;
 }
 
-// d = R * x + t for 3x3 / 3x1 float matrices.  OpenCV evaluates the MatExpr Rcw*x3Dw+tcw as one gemm whose
-// float kernel accumulates in double and rounds once (modules/core/src/matmul.cpp, GEMMSingleMul<float,double>).
-void affine3(const cv::Mat &R, const float x[3], const float t[3], float out[3], bool transpose = false, double alpha = 1.0)
-{
-    for (int r = 0; r < 3; r++) {
-        double s = 0;
-        for (int k = 0; k < 3; k++) s += (double)(transpose ? R.at<float>(k, r) : R.at<float>(r, k)) * (double)x[k];
-        out[r] = (float)(alpha * s + (t ? (double)t[r] : 0.0));
-    }
-}
 }  // namespace
 
 namespace {
@@ -771,14 +733,8 @@ int ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, cv::Mat F
 {
     // ref: src/ORBmatcher.cc:657-827.  Epipole in the second image (:664-671) on the host; the node-grouped search with
     // the epipolar tests and the rotation histogram in one call.
-    const cv::Mat Cw(pKF1->GetCameraCenter()), R2w(pKF2->GetRotation()), t2w(pKF2->GetTranslation());
-    const float cw[3] = {Cw.at<float>(0, 0), Cw.at<float>(1, 0), Cw.at<float>(2, 0)};
-    const float t2[3] = {t2w.at<float>(0, 0), t2w.at<float>(1, 0), t2w.at<float>(2, 0)};
-    float C2[3];
-    affine3(R2w, cw, t2, C2);                                  // C2 = R2w*Cw+t2w
-    const float invz = 1.0f/C2[2];
-    const float ex =pKF2->fx*C2[0]*invz+pKF2->cx;
-    const float ey =pKF2->fy*C2[1]*invz+pKF2->cy;
+    float ex, ey;
+    hipdetail::epipole_in_second(pKF1, pKF2, ex, ey);
 
     const int n1 = pKF1->N, n2 = pKF2->N;
     vMatchedPairs.clear();

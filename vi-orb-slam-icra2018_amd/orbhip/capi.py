@@ -68,6 +68,7 @@ SYMBOLS = [
     "orbhip_frame_build_rgbd",
     "orbhip_init_score", "orbhip_init_score_device",
     "orbhip_pnp_score", "orbhip_pnp_score_device", "orbhip_sim3_score", "orbhip_sim3_score_device",
+    "orbhip_search_for_triangulation_sets",
 ]
 
 
@@ -76,6 +77,7 @@ class FrameParams(C.Structure):   # orbhip_frame_params
                 ("inv_w", C.c_float), ("inv_h", C.c_float), ("levelsup", C.c_int)]
 
 
+TRI_NEIGHBOUR_DTYPE = np.dtype([("key2", "<u8"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")], align=True)   # orbhip_tri_neighbour
 QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("proj_xr", "<f4"), ("min_level", "<i4"),
                         ("max_level", "<i4"), ("angle", "<f4"), ("flags", "<i4")])   # orbhip_proj_query
 Q_ACTIVE, Q_OBSERVED = 1, 2
@@ -188,6 +190,7 @@ def load():
     L.orbhip_debug_path_mask.argtypes = [i32]
     L.orbhip_debug_path_mask.restype = C.c_uint32
     L.orbhip_search_by_bow_sets.argtypes = [vp, C.c_uint64, vp, C.c_uint64, vp, i32, i32, f32, i32, vp, vp, ip]
+    L.orbhip_search_for_triangulation_sets.argtypes = [vp, C.c_uint64, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.orbhip_window_best_set.argtypes = [vp, C.c_uint64, vp, vp, i32, vp, vp, i32, vp, vp]
     L.orbhip_set_info.argtypes = [vp, C.c_uint64, ip, ip, C.POINTER(C.c_uint64)]
     L.orbhip_set_fingerprint.argtypes = [vp, vp, i32]

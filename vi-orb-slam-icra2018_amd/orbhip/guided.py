@@ -9,7 +9,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
-from .capi import GRID_COLS, GRID_ROWS, KP_DTYPE, Q_ACTIVE, Q_OBSERVED, QUERY_DTYPE, _p, check
+from .capi import GRID_COLS, GRID_ROWS, KP_DTYPE, Q_ACTIVE, Q_OBSERVED, QUERY_DTYPE, TRI_NEIGHBOUR_DTYPE, _p, check
 
 f32 = np.float32
 
@@ -186,3 +186,29 @@ def SearchForTriangulation(ctx, kps1_un, desc1, skip1, groups1, kps2_un, desc2, 
                                                       1 if only_stereo else 0, 1 if check_ori else 0, _p(m12), C.byref(nm)),
           ctx.handle, "orbhip_search_for_triangulation")
     return nm.value, m12[:len(kps1_un)].copy()
+
+
+def SearchForTriangulationSets(ctx, key1, skip1, neighbours, scale_factors2, level_sigma2_2, u_right1=None, u_right2=None,
+                               only_stereo=False, check_ori=True):
+    """SearchForTriangulation of the resident set key1 against K resident neighbours in one call
+    (orbhip_search_for_triangulation_sets).  neighbours = K tuples (key2, skip2, F12, ex, ey); u_right2 = None (monocular) or
+    the K mvuRight arrays in neighbour order.  Returns (nmatches[K], matches12[K, n1]); row k is what SearchForTriangulation
+    returns for neighbour k."""
+    skip1 = np.ascontiguousarray(skip1, np.uint8)
+    K, n1 = len(neighbours), len(skip1)
+    nb = np.zeros(K, TRI_NEIGHBOUR_DTYPE)
+    for k, (key2, _, F12, ex, ey) in enumerate(neighbours):
+        nb["key2"][k], nb["F12"][k], nb["ex"][k], nb["ey"][k] = key2, np.asarray(F12, f32).reshape(9), ex, ey
+    skip2 = np.ascontiguousarray(np.concatenate([np.asarray(t[1], np.uint8) for t in neighbours]) if K else np.zeros(0, np.uint8))
+    ur1 = None if u_right1 is None else np.ascontiguousarray(u_right1, f32)
+    ur2 = None if u_right2 is None else np.ascontiguousarray(np.concatenate([np.asarray(u, f32) for u in u_right2]) if K
+                                                             else np.zeros(0, f32))
+    sf = np.ascontiguousarray(scale_factors2, f32)
+    s2 = np.ascontiguousarray(level_sigma2_2, f32)
+    m12 = np.empty((K, n1), np.int32)
+    nm = np.empty(K, np.int32)
+    check(capi.load().orbhip_search_for_triangulation_sets(ctx.handle, int(key1), _p(skip1), _p(ur1), _p(nb), K, _p(skip2), _p(ur2),
+                                                           _p(sf), _p(s2), len(sf), 1 if only_stereo else 0,
+                                                           1 if check_ori else 0, _p(m12), _p(nm)),
+          ctx.handle, "orbhip_search_for_triangulation_sets")
+    return nm, m12

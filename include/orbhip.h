@@ -802,6 +802,55 @@ int orbhip_track_local_points(orbhip_ctx *ctx, uint64_t frame_key, const float *
                               float nnratio, uint64_t *local_keys_out, int cap, int *nlocal, orbhip_local_point *points,
                               int *n_to_match, int32_t *match, int *nmatches);
 
+/* ---- Tracking's other two guided searches on the resident map ----
+ * orbhip_search_last_frame        ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) of TrackWithMotionModel
+ *                                 (ref: src/ORBmatcher.cc:1341-1498): every point the last frame holds, projected with the current
+ *                                 pose and searched in a window on the octaves `motion` allows;
+ * orbhip_search_keyframe_points   SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) of Relocalization
+ *                                 (ref: :1500-1627): the key frame's points that are not in found_keys.
+ * Points come from the store (orbhip_map_*), the key frame's mvpMapPoints from the key-frame table (orbhip_map_kf_*), octaves and
+ * angles of the source features from their resident sets: a camera, the key list, u_right / occupied of the current frame and 16
+ * bytes of counts go up in one block, one block comes back, one synchronisation.
+ *   cur_key       resident set of the current frame, put with a grid; last_key / kf_set_key: resident sets of the source frame
+ *                 (no grid needed; 0 = a frame without features, which no set can hold: n_last == 0 or an empty row then);
+ *                 kf_row_key: the key frame's row in the table, as long as its set
+ *   cam           Rcw, tcw, intrinsics, mbf, bounds, scale_factors / nlevels of the CURRENT frame, th = the th of the call;
+ *                 viewing_cos_limit is not read; the key-frame form also reads Ow and log_scale_factor (PredictScale)
+ *   last_point_keys [n_last]  LastFrame.mvpMapPoints as keys: 0 for NULL and for mvbOutlier; a key the store does not know is
+ *                 inactive.  A point flagged ORBHIP_MP_BAD takes part, as in the reference, which does not test isBad() there
+ *   motion        0 same: octaves [o - 1, o + 1]; 1 forward: [o, ...]; 2 backward: [0, o] (:1351-1365, :1407-1412)
+ *   u_right [n] or NULL (monocular), occupied [n] or NULL as in orbhip_search_by_projection (key-frame form: every feature
+ *                 that holds a point, :1565-1566; it has no u_right because the reference does not test it there)
+ *   queries_out   [n_last] / [row length] or NULL: the queries as the kernel wrote them; inactive ones are all zero
+ *   match [n], *nmatches   as orbhip_search_by_projection defines them with use_ratio = 0 (-1, -2); match[i] indexes the source
+ *                 feature; *n_active = the number of ORBHIP_Q_ACTIVE queries
+ * The arithmetic is the reference's: the camera point is one gemm (double sums, one rounding), invz = (float)(1.0 / (double)z)
+ * -- a double division, not the float division of isInFrustum -- and every other operation an individually rounded float one.
+ * ORBHIP_E_ARG (ORBHIP_E_SIZE for the last), with no output touched: no store (key-frame form: no table), an unknown set, cur_key
+ * without a grid, n_last different from the last set's size, a row whose length differs from its set's, motion outside 0..2,
+ * nlevels outside 1..16, a th that is not finite, a last-frame set with an octave outside [0, nlevels), a current frame too
+ * large for the match table in LDS.  n_last == 0 or an empty row: match all -1, counts 0, nothing is launched.
+ * Divergences from the reference, by design (it reaches undefined behaviour there): a point is inactive when its position, the
+ * reciprocal depth (z == 0), u or v is not finite, when dist3D is 0 or not finite, when mfMaxDistance / dist3D is not finite, or
+ * when the store does not know its key. */
+int orbhip_search_last_frame(orbhip_ctx *ctx, uint64_t cur_key, uint64_t last_key, const uint64_t *last_point_keys, int n_last,
+                             const orbhip_local_camera *cam, int motion, const float *u_right, const uint8_t *occupied,
+                             int check_ori, int th_high, orbhip_proj_query *queries_out, int *n_active, int32_t *match,
+                             int *nmatches);
+int orbhip_search_keyframe_points(orbhip_ctx *ctx, uint64_t cur_key, uint64_t kf_set_key, uint64_t kf_row_key,
+                                  const uint64_t *found_keys, int n_found, const orbhip_local_camera *cam, const uint8_t *occupied,
+                                  int check_ori, int th_high, orbhip_proj_query *queries_out, int *n_active, int32_t *match,
+                                  int *nmatches);
+/* The last-frame form for B frames, laid out as for orbhip_search_local_points_device: d_cam [B], d_slots [B][cap_q]
+ * (orbhip_map_slots; -1 = no point), d_last_kps [B][cap_q] (orbhip_keypoint: octave and angle are read), d_motion [B] (int32),
+ * d_nq [B]; d_queries [B][cap_q] or NULL, d_n_active [B], d_match [B][cap], d_nmatches [B].  No synchronisation.  A source
+ * keypoint whose octave is outside [0, min(nlevels, 16)) is inactive (the host form refuses such a set). */
+int orbhip_search_last_frame_device(orbhip_ctx *ctx, const void *d_kps_un, const void *d_desc, const void *d_counts, int cap, int B,
+                                    const void *d_u_right, const void *d_occupied, float min_x, float min_y, float inv_w,
+                                    float inv_h, const void *d_cell_off, const void *d_cell_idx, const void *d_cam,
+                                    const void *d_slots, const void *d_last_kps, const void *d_motion, const void *d_nq, int cap_q,
+                                    int check_ori, int th_high, void *d_queries, void *d_n_active, void *d_match, void *d_nmatches);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

@@ -9,6 +9,7 @@
 
 #include <map>
 #include <mutex>
+#include <set>
 #include <unordered_map>
 #include <vector>
 
@@ -81,10 +82,26 @@ public:
     int TrackLocalPoints(Frame &F, const std::vector<KeyFrame *> &vpLocalKeyFrames, std::vector<MapPoint *> &vpLocalMapPoints, float th,
                          float viewingCosLimit, int *nToMatch);
 
+    // ---- Tracking's other two projection searches on the resident map (orbhip_search_last_frame,
+    // orbhip_search_keyframe_points) ----
+    // ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) of TrackWithMotionModel (ref: src/ORBmatcher.cc:
+    // 1341-1498): the same return value, and Cur.mvpMapPoints written the same way -- the last point assigned to a feature
+    // stays, a feature whose match the rotation check removed becomes NULL, every other feature is left alone.  Both frames
+    // become resident sets the first time they are searched.  Points of Last that were never Put (Tracking's temporal stereo
+    // points) are put before the call, with one upload; the caller Erases them when it deletes them.
+    int SearchLastFrame(Frame &Cur, const Frame &Last, float th, bool bMono, bool checkOri = true);
+    // ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) of Relocalization (ref: :1500-1627).  The
+    // key frame's points are those of its row in the table (PutKeyFrame / SetMapPoint; put here when it has none yet): equal
+    // to pKF->GetMapPointMatches() under the rule PutKeyFrame states.  Returns and writes as SearchLastFrame.
+    int SearchKeyFramePoints(Frame &Cur, KeyFrame *pKF, const std::set<MapPoint *> &sAlreadyFound, float th, int ORBdist,
+                             bool checkOri = true);
+
     // device of the objects constructed from now on (default 0)
     static void SetDevice(int device);
 
 protected:
+    bool PutLocked(const std::vector<MapPoint *> &vpMPs);      // Put / PutKeyFrame with mMutex held
+    bool PutKeyFrameLocked(KeyFrame *pKF);
     bool EnsureKeyFrames();
     bool VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, KeyFrame *&pReferenceKF);
     bool CollectKeys(const std::vector<KeyFrame *> &vpKFs, std::vector<uint64_t> &kfKeys);

@@ -90,6 +90,12 @@ struct OrbSetView {
     const int32_t *d_cnt, *d_cellOff, *d_cellIdx;
 };
 bool orb_set_grid_view(orbhip_ctx *c, uint64_t key, OrbSetView *v);
+// the keypoint records of a resident set (with or without a grid) and the range of their octaves
+struct OrbSetKps {
+    int n, octMin, octMax;
+    const orbhip_keypoint *d_kps;
+};
+bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v);
 static inline bool grid_params_ok(float inv_w, float inv_h) { return inv_w > 0.f && inv_h > 0.f; }
 
 // Bump allocator over one temporary device block (host-pointer matching entry points).

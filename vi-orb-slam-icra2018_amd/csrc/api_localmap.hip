@@ -4,45 +4,7 @@
 // synchronisation beyond the one that brings its results back.
 #include "api_common.h"
 
-#include <unordered_map>
-
-#define MAP_MAX_POINTS (1 << 24)
-#define MAP_CHUNK 4096        // points per staged upload of put / update_flags / erase
-#define MP_LIVE 0x80u         // (k_localmap.hip)
-#define MP_GEN_SHIFT 8        // bits 8..31 of a flag word: the slot's generation (k_localcollect.hip)
-#define MP_GEN_END (1u << 24)
-#define KF_MAX_KFS (1 << 16)
-#define KF_MAX_ROW (1 << 13)
-#define KF_MAX_ENTRIES ((int64_t)1 << 26)   // 512 MB of rows
-#define KF_MAX_CALL (1u << 24)              // row entries per collect: 65536 block counts for the one-block scan
-
-// the key-frame -> map-point table (orbhip_map_kf_*): device rows (k_localcollect.hip) and their host mirror
-struct OrbKfTable {
-    int maxKfs = 0, maxRow = 0, stride = 0, rowHigh = 0;   // stride = maxRow + 1 entries; rows [0, rowHigh) have been used
-    OrbBlock rows, marks, first, scratch;                  // int2 [maxKfs][stride] | u32 [maxPoints] 0 | u32 [maxPoints] ~0 | collect
-    std::unordered_map<uint64_t, int32_t> rowOf;
-    std::vector<int32_t> freeRows;                         // (taken from the back: row 0 first)
-    std::vector<uint64_t> rowKey;                          // [maxKfs] 0 = free
-    std::vector<std::vector<uint64_t> > entries;           // [maxKfs] the row as uploaded: generation << 32 | slot, ~0 = no point
-};
-
-struct OrbLocalMap {
-    int maxPoints = 0;
-    OrbBlock geoA, geoB, flags, desc;              // [maxPoints] float4 {P, mfMinDistance} | float4 {normal, mfMaxDistance} | u32 | 32 B
-    std::unordered_map<uint64_t, int32_t> slotOf;
-    std::vector<int32_t> freeSlots;                // (taken from the back: slot 0 first)
-    std::vector<uint32_t> gen;                     // [maxPoints] how often the slot has been freed: bits 8..31 of its flag word
-    std::vector<uint64_t> slotKey;                 // [maxPoints] the key in the slot (0 = free)
-    OrbKfTable *kf = nullptr;
-    ~OrbLocalMap() { delete kf; }
-    // the last threshold table (one (mfLogScaleFactor, mnScaleLevels) pair per SLAM session)
-    bool tabValid = false;
-    float tabLogS = 0.f;
-    int tabLevels = 0;
-    float tab[15];
-};
-
-static OrbLocalMap *lmap(orbhip_ctx *c) { return static_cast<OrbLocalMap *>(c->localMap); }
+#include "localmap_store.h"
 
 void orb_localmap_release(orbhip_ctx *c)
 {
@@ -472,8 +434,6 @@ extern "C" int orbhip_map_kf_init(orbhip_ctx *c, int max_kfs, int max_row)
     return ORBHIP_OK;
 }
 
-static OrbKfTable *kf_table(orbhip_ctx *c) { return lmap(c) ? lmap(c)->kf : nullptr; }
-
 extern "C" int orbhip_map_kf_clear(orbhip_ctx *c)
 {
     if (!c) return ORBHIP_E_ARG;
@@ -611,15 +571,6 @@ extern "C" int orbhip_map_kf_erase(orbhip_ctx *c, uint64_t kf_key)
     K->freeRows.push_back(row);
     K->rowOf.erase(it);
     return ORBHIP_OK;
-}
-
-// slots of point keys for the mark scatters: -1 for 0 and for keys the store does not know
-static void kf_mark_slots(const OrbLocalMap *M, const uint64_t *keys, int n, int32_t *slots)
-{
-    for (int i = 0; i < n; i++) {
-        auto it = keys[i] ? M->slotOf.find(keys[i]) : M->slotOf.end();
-        slots[i] = it == M->slotOf.end() ? -1 : it->second;
-    }
 }
 
 extern "C" int orbhip_map_vote(orbhip_ctx *c, int n, const uint64_t *frame_point_keys, uint64_t *kf_keys_out, int32_t *counts_out,

@@ -100,6 +100,14 @@ bool orb_set_grid_view(orbhip_ctx *c, uint64_t key, OrbSetView *v)
     return true;
 }
 
+bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v)
+{
+    OrbSet *s = find_set(c, key);
+    if (!s) return false;
+    *v = {s->n, s->octMin, s->octMax, s->d_kps};
+    return true;
+}
+
 extern "C" int orbhip_set_has(orbhip_ctx *c, uint64_t key, int n)
 {
     if (!c) return 0;

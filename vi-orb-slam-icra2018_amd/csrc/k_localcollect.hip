@@ -12,21 +12,11 @@
 //   k_collect_count / _scan / _write   order-preserving compaction of the candidates with first[slot] == p: block counts, one
 //                               block's scan over them, scatter.  The survivors put first[slot] back to ~0, so no pass over the
 //                               store is ever needed.
-#include "orbhip_internal.h"
+#include "localmap_dev.h"
 #include "wave_ops.h"
 
-#define MP_LIVE 0x80u
 #define COLLECT_BLOCK 256
 #define NO_FIRST 0xFFFFFFFFu
-
-// the slot an entry names, or -1: empty, out of range, erased, re-used (another generation) or bad
-__device__ __forceinline__ int kf_entry_slot(const int2 e, const uint32_t *__restrict__ mflags, int maxPoints)
-{
-    if (e.x < 0 || e.x >= maxPoints) return -1;
-    const uint32_t fl = mflags[e.x];
-    if (!(fl & MP_LIVE) || (fl & ORBHIP_MP_BAD) || (fl >> 8) != (uint32_t)e.y) return -1;
-    return e.x;
-}
 
 __global__ __launch_bounds__(256) void k_mark_add(const int32_t *__restrict__ slots, int n, int maxPoints, uint32_t *__restrict__ marks)
 {

@@ -10,9 +10,7 @@
 // The arithmetic: every cv::Mat expression as OpenCV 2.4 evaluates it -- the gemm in double with one
 // rounding per component, cv::norm and Mat::dot summed in double -- everything else individually rounded float operations.
 // The scale level is a count over a host-built threshold table (api_localmap.hip) instead of a device logf.
-#include "orbhip_internal.h"
-
-#define MP_LIVE 0x80u
+#include "localmap_dev.h"
 
 __global__ __launch_bounds__(256) void k_map_scatter(const int32_t *__restrict__ slot, const float4 *__restrict__ a,
                                                      const float4 *__restrict__ b, const uint32_t *__restrict__ flags,
@@ -40,17 +38,6 @@ __global__ __launch_bounds__(256) void k_map_flags(const int32_t *__restrict__ s
     if (s < 0 || s >= maxPoints) return;
     mflags[s] = flags[i];
 }
-
-// (R row) * P + t of the gemm: products and sums in double, in column order from 0.0, one rounding to float
-__device__ __forceinline__ float gemm_row(const float *__restrict__ R, float t, float x, float y, float z)
-{
-    double s = __dadd_rn(0.0, __dmul_rn((double)R[0], (double)x));
-    s = __dadd_rn(s, __dmul_rn((double)R[1], (double)y));
-    s = __dadd_rn(s, __dmul_rn((double)R[2], (double)z));
-    return (float)__dadd_rn(s, (double)t);
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
 __global__ __launch_bounds__(256) void k_local_frustum(const float4 *__restrict__ geoA, const float4 *__restrict__ geoB,
                                                        const uint32_t *__restrict__ mflags, int maxPoints,

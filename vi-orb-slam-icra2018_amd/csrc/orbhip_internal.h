@@ -526,6 +526,14 @@ void launch_map_flags(hipStream_t s, const int32_t *slot, const uint32_t *flags,
 void launch_local_frustum(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
                           const orbhip_local_camera *cams, const int32_t *slots, const uint8_t *skip, const int32_t *nq, int capQ,
                           int B, orbhip_local_point *points, orbhip_proj_query *queries, int32_t *nToMatch);
+// k_projtrack.hip
+void launch_project_last_frame(hipStream_t s, const void *geoA, const uint32_t *mflags, int maxPoints, const orbhip_local_camera *cams,
+                               const int32_t *slots, const orbhip_keypoint *lastKps, const int32_t *motion, const int32_t *nq, int capQ,
+                               int B, orbhip_proj_query *queries, int32_t *nActive);
+void launch_project_keyframe_points(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
+                                    const uint32_t *marks, const void *rows, int nrows, int stride, int maxRow, const int32_t *rowIdx,
+                                    const orbhip_local_camera *cams, const orbhip_keypoint *kfKps, const int32_t *nq, int capQ, int B,
+                                    orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive);
 // k_localcollect.hip
 void launch_mark_add(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
 void launch_mark_clear(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);

@@ -48,7 +48,13 @@ void LocalMapSearch::Put(MapPoint *pMP) { Put(std::vector<MapPoint *>(1, pMP)); 
 void LocalMapSearch::Put(const std::vector<MapPoint *> &vpMPs)
 {
     std::unique_lock<std::mutex> lock(mMutex);
-    if (!mpCtx || vpMPs.empty()) return;
+    PutLocked(vpMPs);
+}
+
+bool LocalMapSearch::PutLocked(const std::vector<MapPoint *> &vpMPs)
+{
+    if (!mpCtx) return false;
+    if (vpMPs.empty()) return true;
     const size_t n = vpMPs.size();
     std::vector<uint64_t> keys(n);
     std::vector<float> pos(3 * n), nrm(3 * n), mn(n), mx(n);
@@ -71,9 +77,10 @@ void LocalMapSearch::Put(const std::vector<MapPoint *> &vpMPs)
     }
     if (orbhip_map_put(mpCtx, (int)n, keys.data(), pos.data(), nrm.data(), mn.data(), mx.data(), desc.data(), fl.data()) != ORBHIP_OK) {
         hipdetail::Fail("LocalMapSearch::Put", orbhip_last_error(mpCtx));
-        return;
+        return false;
     }
     for (size_t i = 0; i < n; i++) mPointOf[keys[i]] = vpMPs[i];
+    return true;
 }
 
 void LocalMapSearch::UpdateFlags(MapPoint *pMP)

@@ -41,7 +41,12 @@ bool LocalMapSearch::EnsureKeyFrames()
 void LocalMapSearch::PutKeyFrame(KeyFrame *pKF)
 {
     std::unique_lock<std::mutex> lock(mMutex);
-    if (!EnsureKeyFrames()) return;
+    PutKeyFrameLocked(pKF);
+}
+
+bool LocalMapSearch::PutKeyFrameLocked(KeyFrame *pKF)
+{
+    if (!EnsureKeyFrames()) return false;
     const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
     std::vector<uint64_t> row(vpMPs.size(), 0);
     for (size_t i = 0; i < vpMPs.size(); i++) {
@@ -52,9 +57,10 @@ void LocalMapSearch::PutKeyFrame(KeyFrame *pKF)
     }
     if (orbhip_map_kf_put(mpCtx, key_of(pKF), (int)row.size(), row.data()) != ORBHIP_OK) {
         hipdetail::Fail("LocalMapSearch::PutKeyFrame", orbhip_last_error(mpCtx));
-        return;
+        return false;
     }
     mKeyFrameOf[key_of(pKF)] = pKF;
+    return true;
 }
 
 void LocalMapSearch::SetMapPoint(KeyFrame *pKF, size_t idx, MapPoint *pMP)

@@ -64,6 +64,7 @@ SYMBOLS = [
     "orbhip_search_local_points_device",
     "orbhip_map_kf_init", "orbhip_map_kf_clear", "orbhip_map_kf_info", "orbhip_map_kf_put", "orbhip_map_kf_set", "orbhip_map_kf_erase",
     "orbhip_map_vote", "orbhip_map_collect", "orbhip_track_local_points",
+    "orbhip_search_last_frame", "orbhip_search_keyframe_points", "orbhip_search_last_frame_device",
     "orbhip_grey", "orbhip_grey_device", "orbhip_extract_color", "orbhip_rgbd_depth", "orbhip_rgbd_depth_device",
     "orbhip_frame_build_rgbd",
     "orbhip_init_score", "orbhip_init_score_device",
@@ -240,6 +241,10 @@ def load():
     L.orbhip_map_vote.argtypes = [vp, i32, vp, vp, vp, i32, ip]
     L.orbhip_map_collect.argtypes = [vp, i32, vp, vp, i32, ip]
     L.orbhip_track_local_points.argtypes = [vp, u64, vp, vp, vp, i32, vp, i32, vp, f32, vp, i32, ip, vp, ip, vp, ip]
+    L.orbhip_search_last_frame.argtypes = [vp, u64, u64, vp, i32, vp, i32, vp, vp, i32, i32, vp, ip, vp, ip]
+    L.orbhip_search_keyframe_points.argtypes = [vp, u64, u64, u64, vp, i32, vp, vp, i32, i32, vp, ip, vp, ip]
+    L.orbhip_search_last_frame_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
+                                                  i32, i32, i32, vp, vp, vp, vp]
     L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
     L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]

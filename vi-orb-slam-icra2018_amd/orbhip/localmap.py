@@ -15,6 +15,9 @@ CAMERA_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3),
                          ("scale_factors", "<f4", 16), ("log_scale_factor", "<f4"), ("nlevels", "<i4"),
                          ("viewing_cos_limit", "<f4"), ("th", "<f4"), ("level_ratio", "<f4", 15),
                          ("reserved", "<i4")])   # orbhip_local_camera
+QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("proj_xr", "<f4"), ("min_level", "<i4"),
+                        ("max_level", "<i4"), ("angle", "<f4"), ("flags", "<i4")])   # orbhip_proj_query
+MOTION_SAME, MOTION_FORWARD, MOTION_BACKWARD = 0, 1, 2
 POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                         ("in_view", "<i4")])     # orbhip_local_point
 
@@ -171,3 +174,46 @@ class LocalMap:
             e.partial, e.total = keys[:cap].copy(), nl.value
             raise
         return keys[:nl.value].copy(), pts[:nl.value].copy(), ntm.value, nm.value, match[:n].copy()
+
+    # ---- Tracking's other two guided searches on the resident map ----
+    def search_last_frame(self, cur_key, n, last_key, last_point_keys, cam, motion=MOTION_SAME, u_right=None, occupied=None,
+                          check_ori=True, th_high=100, want_queries=True):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) between two resident sets; cam["th"] is the th of the call.
+        last_point_keys: the last frame's points as keys (0: none or an outlier).  Returns (queries or None, n_active, nmatches,
+        match[n] indexing the last frame's features)."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        lk = np.ascontiguousarray(last_point_keys, np.uint64)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, f32)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        q = np.zeros(max(len(lk), 1), QUERY_DTYPE) if want_queries else None
+        match = np.empty(max(n, 1), np.int32)
+        na, nm = C.c_int(), C.c_int()
+        check(self._L.orbhip_search_last_frame(self._ctx.handle, cur_key, last_key, _p(lk), len(lk), _p(cam), motion, _p(ur), _p(occ),
+                                               1 if check_ori else 0, th_high, _p(q), C.byref(na), _p(match), C.byref(nm)),
+              self._ctx.handle, "orbhip_search_last_frame")
+        return (None if q is None else q[:len(lk)].copy()), na.value, nm.value, match[:n].copy()
+
+    def search_keyframe_points(self, cur_key, n, kf_set_key, kf_row_key, nrow, found_keys, cam, occupied=None, check_ori=True,
+                               th_high=100, want_queries=True):
+        """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist): the key frame's row of nrow entries against the
+        resident set cur_key.  Returns (queries or None, n_active, nmatches, match[n] indexing the key frame's features)."""
+        cam = np.ascontiguousarray(cam, CAMERA_DTYPE)
+        fk = np.ascontiguousarray(found_keys, np.uint64)
+        occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+        q = np.zeros(max(nrow, 1), QUERY_DTYPE) if want_queries else None
+        match = np.empty(max(n, 1), np.int32)
+        na, nm = C.c_int(), C.c_int()
+        check(self._L.orbhip_search_keyframe_points(self._ctx.handle, cur_key, kf_set_key, kf_row_key, _p(fk), len(fk), _p(cam), _p(occ),
+                                                    1 if check_ori else 0, th_high, _p(q), C.byref(na), _p(match), C.byref(nm)),
+              self._ctx.handle, "orbhip_search_keyframe_points")
+        return (None if q is None else q[:nrow].copy()), na.value, nm.value, match[:n].copy()
+
+    def search_last_frame_device(self, d_kps, d_desc, d_counts, cap, B, d_u_right, d_occupied, gp, d_cell_off, d_cell_idx, d_cam, d_slots,
+                                 d_last_kps, d_motion, d_nq, cap_q, check_ori, th_high, d_queries, d_n_active, d_match, d_nmatches):
+        """The batched, asynchronous form: every d_* is a device address (int; 0 where the header allows NULL); gp = (min_x,
+        min_y, inv_w, inv_h).  Layouts as in include/orbhip.h.  No synchronisation."""
+        check(self._L.orbhip_search_last_frame_device(self._ctx.handle, d_kps, d_desc, d_counts, cap, B, d_u_right or None,
+                                                      d_occupied or None, gp[0], gp[1], gp[2], gp[3], d_cell_off, d_cell_idx, d_cam,
+                                                      d_slots, d_last_kps, d_motion, d_nq, cap_q, 1 if check_ori else 0, th_high,
+                                                      d_queries or None, d_n_active, d_match, d_nmatches), self._ctx.handle,
+              "orbhip_search_last_frame_device")

@@ -851,6 +851,46 @@ int orbhip_search_last_frame_device(orbhip_ctx *ctx, const void *d_kps_un, const
                                     const void *d_slots, const void *d_last_kps, const void *d_motion, const void *d_nq, int cap_q,
                                     int check_ori, int th_high, void *d_queries, void *d_n_active, void *d_match, void *d_nmatches);
 
+/* ---- ORBmatcher::Fuse for LocalMapping::SearchInNeighbors on the resident map ----
+ * SearchInNeighbors (ref: src/LocalMapping.cc:2514-2594) calls Fuse(pKFi, vpMapPointMatches) (ref: src/ORBmatcher.cc:825-975) once
+ * per target key frame -- 40 to 100 calls -- and then Fuse(mpCurrentKeyFrame, vpFuseCandidates) once.  Everything those loops read
+ * is resident: the points in the store, mvpMapPoints of every key frame in the key-frame table, the targets' features in their sets.
+ *   orbhip_fuse_row      the first pass: the entries of key frame src_row_key's row, in feature order, projected into K targets and
+ *                        searched in each target's window, in one call;
+ *   orbhip_fuse_collect  the second pass: orbhip_map_collect over kf_keys (= vpFuseCandidates element for element), every candidate
+ *                        that the row of cur_row_key already holds inactive (IsInKeyFrame), projected and searched in the one target.
+ * Both return, per (target, point), what the loop of :887-950 finds: best_idx / best_dist as orbhip_window_best defines them with
+ * the chi-square gate on (-1 / 256: inactive, or no feature closer than 256).  The caller applies <= TH_LOW and the map edits in
+ * the reference's order, re-reading isBad() and IsInKeyFrame() there (the drop-in: LocalMapSearch::FuseInTargets / FuseCandidates).
+ * Row k equals what the host projection followed by orbhip_window_best_set gives for target k on the store as it stands at the call.
+ *   targets [K]   a key may repeat; cam.viewing_cos_limit is not read, cam.level_ratio is filled by the call
+ *   skip          [K][n] or NULL: skip[k][i] != 0 = IsInKeyFrame(target k) as the caller knows it; n = the length of the source row
+ *   u_right       the targets' mvuRight one after the other, each as long as its set (fuse_collect: the one target's), or NULL
+ *                 for monocular key frames; a feature with u_right >= 0 takes the 7.8 gate over (u, v, proj_xr), else 5.99
+ *   queries_out   [K][n] / [cap] or NULL: the queries as the kernel wrote them; inactive ones are all zero
+ *   best_idx, best_dist [K][n] / [cap]; n_active [K] / one int: the number of ORBHIP_Q_ACTIVE queries per target
+ *   keys_out [cap], *ncand   as orbhip_map_collect.  ORBHIP_E_CAPACITY when *ncand exceeds cap: the first cap keys are filled, *ncand
+ *                 has the number and *n_active is 0; nothing else is written
+ * The arithmetic is Fuse's, not the frame searches': invz = 1 / z in float, x = xc * invz and then u = fx * x + cx (each operation
+ * rounded), KeyFrame::IsInImage's half-open bounds (u < max_x), PO . normal in double against 0.5 * (double)dist3D.
+ * K == 0 returns ORBHIP_OK and writes nothing.  An empty source row / no candidates: counts 0, nothing is launched.
+ * ORBHIP_E_ARG, with no output touched: no store or table, an unknown row or set, a target without a grid, K < 0, more distinct set
+ * keys than the set limit in force (orbhip_set_limit), nlevels outside 1..16, a th that is not finite.  ORBHIP_E_SIZE, likewise:
+ * K above 65535, K * n beyond 2^24, a target set of 2^20 features or more, more than 2^24 row entries among kf_keys.
+ * Divergences from the reference, by design: a point with dist3D == 0 or not finite, with a non-finite mfMaxDistance / dist3D, or
+ * whose entry does not resolve (empty, erased, re-used slot, ORBHIP_MP_BAD) is inactive. */
+typedef struct orbhip_fuse_target {
+    uint64_t set_key;            /* resident set of the target key frame, put with a grid */
+    orbhip_local_camera cam;     /* the TARGET key frame: Rcw, tcw, Ow, intrinsics, mbf, bounds, scale_factors,
+                                    log_scale_factor, nlevels, th; level_ratio is filled by the call */
+    float inv_level_sigma2[16];  /* KeyFrame::mvInvLevelSigma2 */
+} orbhip_fuse_target;
+int orbhip_fuse_row(orbhip_ctx *ctx, uint64_t src_row_key, const orbhip_fuse_target *targets, int K, const uint8_t *skip,
+                    const float *u_right, orbhip_proj_query *queries_out, int32_t *best_idx, int32_t *best_dist, int32_t *n_active);
+int orbhip_fuse_collect(orbhip_ctx *ctx, const orbhip_fuse_target *target, uint64_t cur_row_key, int nkf, const uint64_t *kf_keys,
+                        const float *u_right, uint64_t *keys_out, int cap, int *ncand, orbhip_proj_query *queries_out,
+                        int32_t *best_idx, int32_t *best_dist, int32_t *n_active);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

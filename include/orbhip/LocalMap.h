@@ -7,10 +7,12 @@
 #ifndef ORBHIP_LOCALMAP_H
 #define ORBHIP_LOCALMAP_H
 
+#include <cstdint>
 #include <map>
 #include <mutex>
 #include <set>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #ifdef ORBHIP_WITH_REFERENCE_HEADERS
@@ -96,6 +98,23 @@ public:
     int SearchKeyFramePoints(Frame &Cur, KeyFrame *pKF, const std::set<MapPoint *> &sAlreadyFound, float th, int ORBdist,
                              bool checkOri = true);
 
+    // ---- ORBmatcher::Fuse for LocalMapping::SearchInNeighbors on the resident map (orbhip_fuse_row, orbhip_fuse_collect;
+    // DESIGN.md section 17) ----
+    // The first loop of SearchInNeighbors (ref: src/LocalMapping.cc:2549-2556): matcher.Fuse(pKFi, pKF->GetMapPointMatches(), th)
+    // for every pKFi of vpTargetKFs, in that order, with the same map edits (AddObservation / AddMapPoint / Replace) and the same
+    // return values, one per target.  All targets are projected and searched in one device call (64 targets at a time beyond
+    // that); the results are then applied target by target and point by point, re-reading isBad(), IsInKeyFrame() and what the
+    // feature holds at that moment, and a point whose descriptor changed because it survived a Replace in an earlier target is
+    // searched again, with its new descriptor, before a later target is applied.  pKF's points are those of its row in the table
+    // (put here when it has none yet) and must have been Put; the targets' features become resident sets the first time.
+    std::vector<int> FuseInTargets(KeyFrame *pKF, const std::vector<KeyFrame *> &vpTargetKFs, float th = 3.0);
+    // The second loop (ref: :2558-2581): vpFuseCandidates = the points of vpTargetKFs, each once, bad ones left out, fused into
+    // pKF with matcher.Fuse(pKF, vpFuseCandidates, th).  The union is built on the device and never leaves it except as the list
+    // the results are applied to.  Returns Fuse's return value.
+    int FuseCandidates(KeyFrame *pKF, const std::vector<KeyFrame *> &vpTargetKFs, float th = 3.0);
+    // Both bring the resident state up to date with every edit they make: the rows of the key frames a replaced point was
+    // observed in, its flags, the survivor's descriptor and flags, the row entry and the flags of an added observation.
+
     // device of the objects constructed from now on (default 0)
     static void SetDevice(int device);
 
@@ -105,6 +124,15 @@ protected:
     bool EnsureKeyFrames();
     bool VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, KeyFrame *&pReferenceKF);
     bool CollectKeys(const std::vector<KeyFrame *> &vpKFs, std::vector<uint64_t> &kfKeys);
+    // Fuse's apply loop over one target (ref: src/ORBmatcher.cc:951-972) and the resident state behind it (LocalMapFuse.cc)
+    struct FuseEdits {
+        std::set<MapPoint *> put, flags;
+        std::map<MapPoint *, std::vector<unsigned char> > survivors; // of a Replace: the descriptor each had at the device call
+        std::set<std::pair<KeyFrame *, size_t> > entries;           // (key frame, feature) whose row entry may have changed
+    };
+    int ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMPs, const int32_t *bestIdx, const int32_t *bestDist, FuseEdits &edits);
+    bool FlushFuse(FuseEdits &edits);
+    bool EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey);
 
     orbhip_ctx *mpCtx;
     std::mutex mMutex;
@@ -112,6 +140,8 @@ protected:
     std::map<uint64_t, KeyFrame *> mKeyFrameOf;
     bool mbKeyFrames = false;
     size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
+    size_t mnLastCandidates = 0;
+    bool mbFuseSets = false;                   // the set limit has been raised for the targets of FuseInTargets
 };
 
 }  // namespace ORB_SLAM2

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <map>
 #include <set>
+#include <utility>
 #include <vector>
 
 #include "cvlite.h"
@@ -63,6 +64,13 @@ public:
     void Replace(MapPoint *pMP);
     MapPoint *GetReplaced() { return mpReplaced; }
     void SetDescriptor(const cv::Mat &d) { mDescriptor = d.clone(); }   // mDescriptor is protected in the reference
+    // ref: src/MapPoint.cc:283-349 (body below KeyFrame): the observed descriptor with the least median distance to the others.
+    // The reference walks its observation map by heap address; here the observations are taken in ascending KeyFrame::mnId
+    // order, so that equal medians resolve the same way in every process.  The reference's Replace ends in this call
+    // (src/MapPoint.cc:227); here it does so only while RecomputeOnReplace() is set, which the programs that test
+    // LocalMapSearch::FuseInTargets do (a survivor's descriptor then changes between two targets, as in the reference).
+    void ComputeDistinctiveDescriptors();
+    static bool &RecomputeOnReplace() { static bool b = false; return b; }
 
     // ref: include/MapPoint.h "long unsigned int mnId; static long unsigned int nNextId;": mnId + 1 is the key under which
     // LocalMapSearch keeps the point resident on the device
@@ -293,6 +301,52 @@ inline void MapPoint::Replace(MapPoint *pMP)
         else
             pKF->EraseMapPointMatch(mit->second);
     }
+    if(RecomputeOnReplace())
+        pMP->ComputeDistinctiveDescriptors();
+}
+
+inline void MapPoint::ComputeDistinctiveDescriptors()
+{
+    if(mbBad || mObservations.empty())
+        return;
+    std::vector<std::pair<long unsigned int, const unsigned char *> > rows;
+    for(std::map<KeyFrame *, size_t>::iterator mit=mObservations.begin(), mend=mObservations.end(); mit!=mend; mit++)
+        if(!mit->first->isBad())
+            rows.push_back(std::make_pair(mit->first->mnId, mit->first->mDescriptors.ptr((int)mit->second)));
+    if(rows.empty())
+        return;
+    for(size_t i=1; i<rows.size(); i++)          // ascending mnId (insertion sort: a handful of observations)
+        for(size_t j=i; j>0 && rows[j].first<rows[j-1].first; j--)
+            std::swap(rows[j], rows[j-1]);
+    const size_t N = rows.size();
+    std::vector<std::vector<int> > Distances(N, std::vector<int>(N, 0));
+    for(size_t i=0; i<N; i++)
+        for(size_t j=i+1; j<N; j++)
+        {
+            int dist = 0;
+            for(int b=0; b<32; b++)
+                dist += __builtin_popcount((unsigned)(rows[i].second[b] ^ rows[j].second[b]));
+            Distances[i][j] = Distances[j][i] = dist;
+        }
+    int BestMedian = 0x7FFFFFFF;
+    size_t BestIdx = 0;
+    for(size_t i=0; i<N; i++)
+    {
+        std::vector<int> vDists(Distances[i]);
+        for(size_t a=1; a<N; a++)
+            for(size_t b=a; b>0 && vDists[b]<vDists[b-1]; b--)
+                std::swap(vDists[b], vDists[b-1]);
+        const int median = vDists[(size_t)(0.5*(N-1))];
+        if(median<BestMedian)
+        {
+            BestMedian = median;
+            BestIdx = i;
+        }
+    }
+    cv::Mat d(1, 32, CV_8U);
+    for(int b=0; b<32; b++)
+        d.ptr(0)[b] = rows[BestIdx].second[b];
+    mDescriptor = d;
 }
 
 }  // namespace ORB_SLAM2

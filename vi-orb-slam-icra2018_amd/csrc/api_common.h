@@ -96,6 +96,7 @@ struct OrbSetKps {
     const orbhip_keypoint *d_kps;
 };
 bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v);
+int orb_set_limit_in_force(orbhip_ctx *c);   // orbhip_set_limit: how many sets a call may name
 static inline bool grid_params_ok(float inv_w, float inv_h) { return inv_w > 0.f && inv_h > 0.f; }
 
 // Bump allocator over one temporary device block (host-pointer matching entry points).

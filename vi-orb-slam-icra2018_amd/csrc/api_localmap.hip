@@ -530,11 +530,21 @@ extern "C" int orbhip_map_kf_set(orbhip_ctx *c, uint64_t kf_key, int m, const in
         if (idx[j] < 0 || idx[j] >= (int)ent.size()) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: an index outside the row");
         if (!kf_resolve(M, point_keys[j], &ent[idx[j]])) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point key is not in the store");
     }
-    for (int j = 0; j < m; j++) {   // (a later entry of the call may have emptied the index an earlier one filled: compare what stays)
-        const uint64_t e = ent[idx[j]];
-        if (e == KF_NONE) continue;
-        for (size_t i = 0; i < ent.size(); i++)
-            if (ent[i] == e && (int)i != idx[j]) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point appears twice in the row");
+    {   // a point twice in the row as it will be (a later entry of the call may have emptied the index an earlier one filled:
+        // compare what stays).  One pass over the row against the sorted values of the changed indices: a Fuse pass sets a
+        // hundred entries of a row at a time.
+        std::vector<uint8_t> touched(ent.size(), 0);
+        std::vector<uint64_t> vals;
+        for (int j = 0; j < m; j++) {
+            if (touched[idx[j]]) continue;
+            touched[idx[j]] = 1;
+            if (ent[idx[j]] != KF_NONE) vals.push_back(ent[idx[j]]);
+        }
+        std::sort(vals.begin(), vals.end());
+        bool twice = std::adjacent_find(vals.begin(), vals.end()) != vals.end();
+        for (size_t i = 0; i < ent.size() && !twice; i++)
+            twice = !touched[i] && ent[i] != KF_NONE && std::binary_search(vals.begin(), vals.end(), ent[i]);
+        if (twice) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point appears twice in the row");
     }
     HIPCHK(c, orb_enter(c));
     Packed P(c);
@@ -613,48 +623,6 @@ extern "C" int orbhip_map_vote(orbhip_ctx *c, int n, const uint64_t *frame_point
     *nout = (int)v.size();
     for (int k = 0; k < (int)v.size() && k < cap; k++) kf_keys_out[k] = v[k].first, counts_out[k] = v[k].second;
     if ((int)v.size() > cap) return fail(c, ORBHIP_E_CAPACITY, "orbhip_map_vote: more key frames than cap (*nout has the number)");
-    return ORBHIP_OK;
-}
-
-// What a collect needs on the device: the rows of the call and their offsets, uploaded with the caller's block; the scratch
-struct KfCall {
-    uint32_t total = 0;   // candidates
-    const int32_t *d_rowIdx = nullptr;
-    const uint32_t *d_off = nullptr;
-    int32_t *d_cand = nullptr, *d_blockCnt = nullptr;
-    uint8_t *d_skip = nullptr;   // [capOut] (the fused call)
-};
-
-// validates the key frames and sizes the candidate list (no device work)
-static int kf_call_rows(orbhip_ctx *c, OrbKfTable *K, const char *who, int nkf, const uint64_t *kf_keys, std::vector<int32_t> &rowIdx,
-                        std::vector<uint32_t> &off)
-{
-    rowIdx.resize(nkf);
-    off.resize(nkf + 1);
-    uint64_t total = 0;
-    for (int k = 0; k < nkf; k++) {
-        auto it = K->rowOf.find(kf_keys[k]);
-        if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": unknown key frame");
-        rowIdx[k] = it->second;
-        off[k] = (uint32_t)total;
-        total += K->entries[it->second].size();
-        if (total > KF_MAX_CALL) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": more than 2^24 row entries in one call");
-    }
-    off[nkf] = (uint32_t)total;
-    return ORBHIP_OK;
-}
-
-static int kf_call_scratch(orbhip_ctx *c, OrbKfTable *K, KfCall &Q, int capOut)
-{
-    const size_t candBytes = align_up((size_t)Q.total * 4, 256), cntBytes = align_up((size_t)collect_blocks(Q.total) * 4, 256);
-    const size_t need = candBytes + cntBytes + (size_t)capOut + 256;
-    if (K->scratch.bytes() < need) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, K->scratch.grow(need, need + need / 2));
-    }
-    Q.d_cand = K->scratch.as<int32_t>();
-    Q.d_blockCnt = (int32_t *)(K->scratch.as<uint8_t>() + candBytes);
-    Q.d_skip = K->scratch.as<uint8_t>() + candBytes + cntBytes;
     return ORBHIP_OK;
 }
 

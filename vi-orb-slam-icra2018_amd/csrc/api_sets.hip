@@ -108,6 +108,8 @@ bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v)
     return true;
 }
 
+int orb_set_limit_in_force(orbhip_ctx *c) { return table(c)->limit; }
+
 extern "C" int orbhip_set_has(orbhip_ctx *c, uint64_t key, int n)
 {
     if (!c) return 0;

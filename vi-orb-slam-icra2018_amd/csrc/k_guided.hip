@@ -16,24 +16,12 @@
 //                   accepted in order until a row considered a feature that an earlier row of the group has just
 //                   closed (that row is redone); then the rotation histogram.  A point with more candidates than
 //                   the list holds is rescanned exactly as the reference does it.
-#include "orbhip_internal.h"
-#include "wave_ops.h"
+#include "localmap_dev.h"   // GridParams, window_cells, WAVE_LDS_SYNC, window_row_best
 
 #define GCOLS ORBHIP_GRID_COLS
 #define GROWS ORBHIP_GRID_ROWS
 #define GCELLS ORBHIP_GRID_CELLS
 #define PROJ_K 32   // candidate slots per point (one 64-point chunk of lists = 8 KB of LDS)
-
-#define WAVE_LDS_SYNC()                                        \
-    do {                                                       \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
-        __builtin_amdgcn_wave_barrier();                       \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); \
-    } while (0)
-
-struct GridParams {
-    float minX, minY, invW, invH;
-};
 
 __device__ __forceinline__ int grid_cell(const GridParams &gp, float x, float y)
 {
@@ -148,21 +136,6 @@ __global__ __launch_bounds__(NT) void k_grid_build(const orbhip_keypoint *__rest
             if (cellIdx2) cellIdx2[j] = s_idx[j];
         }
     }
-}
-
-// The window of GetFeaturesInArea in cells; false = the early returns of :676-691.
-__device__ __forceinline__ bool window_cells(const GridParams &gp, float x, float y, float r, int &x0, int &x1, int &y0,
-                                             int &y1)
-{
-    x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, gp.minX), r), gp.invW)));
-    if (x0 >= GCOLS) return false;
-    x1 = min(GCOLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, gp.minX), r), gp.invW)));
-    if (x1 < 0) return false;
-    y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, gp.minY), r), gp.invH)));
-    if (y0 >= GROWS) return false;
-    y1 = min(GROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, gp.minY), r), gp.invH)));
-    if (y1 < 0) return false;
-    return true;
 }
 
 // Calls f(feature index, octave) for the features of GetFeaturesInArea(q.u, q.v, q.radius, q.min_level,
@@ -489,58 +462,11 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
             const float *UR = uRight ? uRight + (size_t)b * cap : nullptr;
             const float4 *R = rec + (size_t)b * cap;
             const int32_t *O = cellOff + (size_t)b * (GCELLS + 1);
-            int seen = 0;
-            for (int cb = x0; cb <= x1; cb += 16) {
-                const int ix = cb + gl;
-                const int s = ix <= x1 ? O[ix * GROWS + y0] : 0, e = ix <= x1 ? O[ix * GROWS + y1 + 1] : 0;
-                const int incl = row_incl_scan(e - s);
-                s_start[row][gl] = s;
-                s_excl[row][gl + 1] = incl;
-                if (gl == 0) s_excl[row][0] = 0;
-                WAVE_LDS_SYNC();
-                const int total = s_excl[row][16];
-                for (int r = gl; r < total; r += 16) {
-                    int c = 0;
-#pragma unroll
-                    for (int h = 8; h > 0; h >>= 1)
-                        if (s_excl[row][c + h] <= r) c += h;
-                    const float4 rr = R[s_start[row][c] + (r - s_excl[row][c])];
-                    const int w = __float_as_int(rr.z), oct = w & 255, idx = w >> 8;
-                    if (!(fabsf(__fsub_rn(rr.x, q.u)) < q.radius && fabsf(__fsub_rn(rr.y, q.v)) < q.radius)) continue;
-                    if (oct < q.min_level || oct > q.max_level) continue;
-                    if (gate.on) {
-                        const float ex = __fsub_rn(q.u, rr.x), ey = __fsub_rn(q.v, rr.y);
-                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        const float ur = UR ? UR[idx] : -1.0f;
-                        double lim = 5.99;
-                        if (ur >= 0) {
-                            const float er = __fsub_rn(q.proj_xr, ur);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            lim = 7.8;
-                        }
-                        if ((double)__fmul_rn(e2, gate.invSigma2[oct & 15]) > lim) continue;
-                    }
-                    const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
-                    const int k = (d << 20) | (seen + r);
-                    if (d < 256 && k < key) {
-                        key = k;
-                        myIdx = idx;
-                    }
-                }
-                seen += total;
-                WAVE_LDS_SYNC();
-            }
+            window_row_best(q, x0, x1, y0, y1, a0, a1, D, UR, R, O, gate.on != 0, [&gate](int oct) { return gate.invSigma2[oct & 15]; },
+                            s_start[row], s_excl[row], gl, key, myIdx);
         }
     }
-    const int k1 = row_min_inactive_ok(key);
-    if (key == k1 && k1 != 0x7FFFFFFF) {   // one lane: positions are unique
-        bestIdx[(size_t)b * capQ + iq] = myIdx;
-        bestDist[(size_t)b * capQ + iq] = k1 >> 20;
-    }
-    if (k1 == 0x7FFFFFFF && gl == 0) {
-        bestIdx[(size_t)b * capQ + iq] = -1;
-        bestDist[(size_t)b * capQ + iq] = 256;
-    }
+    window_row_store(key, myIdx, gl, bestIdx + (size_t)b * capQ + iq, bestDist + (size_t)b * capQ + iq);
 }
 
 template <bool QIND>

@@ -34,13 +34,6 @@ __device__ __forceinline__ bool project_point(const orbhip_local_camera &C, cons
     return true;
 }
 
-// active queries of frame b: a ballot and one atomic per wave (every lane of the block arrives here)
-__device__ __forceinline__ void count_active(bool active, int32_t *__restrict__ counter)
-{
-    const unsigned long long m = __ballot(active);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(counter, __popcll(m));
-}
-
 __global__ __launch_bounds__(256) void k_project_last_frame(const float4 *__restrict__ geoA, const uint32_t *__restrict__ mflags,
                                                             int maxPoints, const orbhip_local_camera *__restrict__ cams,
                                                             const int32_t *__restrict__ slots,

@@ -1,5 +1,6 @@
 // localmap_store.h -- the host side of the resident map-point store and of the key-frame table, shared by the api_*.hip files
-// that search them (api_localmap.hip, api_projtrack.hip): device blocks and the key -> slot / key -> row tables.
+// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip): device blocks, the key -> slot / key -> row tables and
+// what a call over several rows of the table (the ordered union) sets up.
 #ifndef ORBHIP_LOCALMAP_STORE_H
 #define ORBHIP_LOCALMAP_STORE_H
 #include "api_common.h"
@@ -52,6 +53,48 @@ static inline void kf_mark_slots(const OrbLocalMap *M, const uint64_t *keys, int
         auto it = keys[i] ? M->slotOf.find(keys[i]) : M->slotOf.end();
         slots[i] = it == M->slotOf.end() ? -1 : it->second;
     }
+}
+
+// What a collect needs on the device: the rows of the call and their offsets, uploaded with the caller's block; the scratch
+struct KfCall {
+    uint32_t total = 0;   // candidates
+    const int32_t *d_rowIdx = nullptr;
+    const uint32_t *d_off = nullptr;
+    int32_t *d_cand = nullptr, *d_blockCnt = nullptr;
+    uint8_t *d_skip = nullptr;   // [capOut] (the fused call)
+};
+
+// validates the key frames and sizes the candidate list (no device work)
+static inline int kf_call_rows(orbhip_ctx *c, OrbKfTable *K, const char *who, int nkf, const uint64_t *kf_keys, std::vector<int32_t> &rowIdx,
+                        std::vector<uint32_t> &off)
+{
+    rowIdx.resize(nkf);
+    off.resize(nkf + 1);
+    uint64_t total = 0;
+    for (int k = 0; k < nkf; k++) {
+        auto it = K->rowOf.find(kf_keys[k]);
+        if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": unknown key frame");
+        rowIdx[k] = it->second;
+        off[k] = (uint32_t)total;
+        total += K->entries[it->second].size();
+        if (total > KF_MAX_CALL) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": more than 2^24 row entries in one call");
+    }
+    off[nkf] = (uint32_t)total;
+    return ORBHIP_OK;
+}
+
+static inline int kf_call_scratch(orbhip_ctx *c, OrbKfTable *K, KfCall &Q, int capOut)
+{
+    const size_t candBytes = align_up((size_t)Q.total * 4, 256), cntBytes = align_up((size_t)collect_blocks(Q.total) * 4, 256);
+    const size_t need = candBytes + cntBytes + (size_t)capOut + 256;
+    if (K->scratch.bytes() < need) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, K->scratch.grow(need, need + need / 2));
+    }
+    Q.d_cand = K->scratch.as<int32_t>();
+    Q.d_blockCnt = (int32_t *)(K->scratch.as<uint8_t>() + candBytes);
+    Q.d_skip = K->scratch.as<uint8_t>() + candBytes + cntBytes;
+    return ORBHIP_OK;
 }
 
 #endif

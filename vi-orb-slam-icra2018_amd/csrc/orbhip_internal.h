@@ -534,6 +534,18 @@ void launch_project_keyframe_points(hipStream_t s, const void *geoA, const void 
                                     const uint32_t *marks, const void *rows, int nrows, int stride, int maxRow, const int32_t *rowIdx,
                                     const orbhip_local_camera *cams, const orbhip_keypoint *kfKps, const int32_t *nq, int capQ, int B,
                                     orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive);
+// k_fuse.hip
+void launch_project_fuse_row(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints, const void *row,
+                             int rowCap, const uint8_t *skip, const orbhip_local_camera *cams, int capQ, int K,
+                             orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive);
+void launch_project_fuse_list(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
+                              const uint32_t *marks, const int32_t *slots, const int32_t *nq, const orbhip_local_camera *cam, int capQ,
+                              orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive);
+size_t fuse_target_bytes();   // one per-target record of the search, written by fuse_target_fill
+void fuse_target_fill(void *dst, const void *kps, const void *desc, const int32_t *cellOff, const int32_t *cellIdx, void *rec,
+                      const float *uRight, float minX, float minY, float invW, float invH, int n, const float *invSigma2);
+void launch_window_best_sets(hipStream_t s, const void *targets, int K, int maxN, const orbhip_proj_query *queries, const void *mdesc,
+                             const int32_t *qslot, int capQ, int32_t *bestIdx, int32_t *bestDist);
 // k_localcollect.hip
 void launch_mark_add(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
 void launch_mark_clear(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);

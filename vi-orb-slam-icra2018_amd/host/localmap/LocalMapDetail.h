@@ -1,4 +1,4 @@
-// LocalMapDetail.h -- what LocalMap.cc and LocalMapCollect.cc share: keys and flags of a MapPoint, the frame as a resident
+// LocalMapDetail.h -- what LocalMap.cc, LocalMapCollect.cc, LocalMapProjTrack.cc and LocalMapFuse.cc share: keys and flags of a MapPoint, the frame as a resident
 // set, the camera block of a search and the write-back of its results (ref: src/Tracking.cc:2336-2364, src/Frame.cc:613-669,
 // src/ORBmatcher.cc:45-129).
 #ifndef ORBHIP_LOCALMAP_DETAIL_H
@@ -17,6 +17,8 @@ namespace localmapdetail
 {
 inline uint64_t key_of(MapPoint *pMP) { return (uint64_t)pMP->mnId + 1; }
 inline uint64_t key_of(KeyFrame *pKF) { return (uint64_t)pKF->mnId + 1; }
+// a key frame's feature set, apart from the frames' (Frame::mnId + 1)
+inline uint64_t set_key_of(KeyFrame *pKF) { return (1ull << 62) | key_of(pKF); }
 inline uint8_t flags_of(MapPoint *pMP)
 {
     return (uint8_t)((pMP->Observations() > 0 ? ORBHIP_MP_OBSERVED : 0) | (pMP->isBad() ? ORBHIP_MP_BAD : 0));

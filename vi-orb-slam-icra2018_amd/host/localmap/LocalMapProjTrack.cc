@@ -16,8 +16,6 @@ using localmapdetail::key_of;
 
 namespace
 {
-const uint64_t KF_SET_KEY = 1ull << 62;   // a key frame's feature set, apart from the frames' (Frame::mnId + 1)
-
 bool has_pyramid(const Frame &F) { return F.mnScaleLevels >= 1 && F.mnScaleLevels <= 16 && (int)F.mvScaleFactors.size() >= F.mnScaleLevels; }
 
 // match[] of the window search -> Cur.mvpMapPoints the way the reference's loops write it (ref: :1452, :1489, :1579, :1617)
@@ -92,7 +90,7 @@ int LocalMapSearch::SearchKeyFramePoints(Frame &Cur, KeyFrame *pKF, const std::s
     uint64_t curKey = 0;
     if (!localmapdetail::put_frame(mpCtx, Cur, &curKey))
         return hipdetail::Fail("LocalMapSearch::SearchKeyFramePoints (orbhip_set_put)", orbhip_last_error(mpCtx)), 0;
-    const uint64_t kfSetKey = KF_SET_KEY | key_of(pKF);
+    const uint64_t kfSetKey = localmapdetail::set_key_of(pKF);
     if (!hipdetail::ensure_set(mpCtx, kfSetKey, *pKF, pKF->mvKeysUn, pKF->mnMinX, pKF->mnMinY, pKF->mfGridElementWidthInv,
                                pKF->mfGridElementHeightInv, NULL))
         return hipdetail::Fail("LocalMapSearch::SearchKeyFramePoints (key frame set)", orbhip_last_error(mpCtx)), 0;

@@ -70,6 +70,7 @@ SYMBOLS = [
     "orbhip_init_score", "orbhip_init_score_device",
     "orbhip_pnp_score", "orbhip_pnp_score_device", "orbhip_sim3_score", "orbhip_sim3_score_device",
     "orbhip_search_for_triangulation_sets",
+    "orbhip_fuse_row", "orbhip_fuse_collect",
 ]
 
 
@@ -245,6 +246,8 @@ def load():
     L.orbhip_search_keyframe_points.argtypes = [vp, u64, u64, u64, vp, i32, vp, vp, i32, i32, vp, ip, vp, ip]
     L.orbhip_search_last_frame_device.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, f32, f32, f32, f32, vp, vp, vp, vp, vp, vp, vp,
                                                   i32, i32, i32, vp, vp, vp, vp]
+    L.orbhip_fuse_row.argtypes = [vp, u64, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbhip_fuse_collect.argtypes = [vp, vp, u64, i32, vp, vp, vp, i32, ip, vp, vp, vp, ip]
     L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
     L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]

@@ -18,6 +18,7 @@ CAMERA_DTYPE = np.dtype([("Rcw", "<f4", 9), ("tcw", "<f4", 3), ("Ow", "<f4", 3),
 QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("proj_xr", "<f4"), ("min_level", "<i4"),
                         ("max_level", "<i4"), ("angle", "<f4"), ("flags", "<i4")])   # orbhip_proj_query
 MOTION_SAME, MOTION_FORWARD, MOTION_BACKWARD = 0, 1, 2
+FUSE_TARGET_DTYPE = np.dtype([("set_key", "<u8"), ("cam", CAMERA_DTYPE), ("inv_level_sigma2", "<f4", 16)], align=True)   # orbhip_fuse_target
 POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                         ("in_view", "<i4")])     # orbhip_local_point
 
@@ -33,6 +34,16 @@ def camera(Rcw, tcw, Ow, fx, fy, cx, cy, mbf, bounds, scale_factors, log_scale_f
     c["nlevels"], c["log_scale_factor"] = len(sf), log_scale_factor
     c["viewing_cos_limit"], c["th"] = viewing_cos_limit, th
     return c
+
+
+def fuse_target(set_key, cam, inv_level_sigma2):
+    """One orbhip_fuse_target record: the target's resident set, its camera record (camera(); th = the th of Fuse) and
+    KeyFrame::mvInvLevelSigma2."""
+    t = np.zeros(1, FUSE_TARGET_DTYPE)
+    t["set_key"], t["cam"] = set_key, np.ascontiguousarray(cam, CAMERA_DTYPE)[0]
+    sg = np.asarray(inv_level_sigma2, f32)
+    t["inv_level_sigma2"][0][:len(sg)] = sg
+    return t
 
 
 def predict_scale_table(log_scale_factor, nlevels):
@@ -207,6 +218,40 @@ class LocalMap:
                                                     1 if check_ori else 0, th_high, _p(q), C.byref(na), _p(match), C.byref(nm)),
               self._ctx.handle, "orbhip_search_keyframe_points")
         return (None if q is None else q[:nrow].copy()), na.value, nm.value, match[:n].copy()
+
+    # ---- ORBmatcher::Fuse for LocalMapping::SearchInNeighbors on the resident map ----
+    def fuse_row(self, src_row_key, n, targets, skip=None, u_right=None, want_queries=True):
+        """The first pass: the n entries of key frame src_row_key's row into the K targets (fuse_targets).  skip: [K][n] or None;
+        u_right: the targets' arrays one after the other, or None.  Returns (queries [K][n] or None, best_idx, best_dist, n_active [K])."""
+        t = np.ascontiguousarray(targets, FUSE_TARGET_DTYPE)
+        K = len(t)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, n)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, f32)
+        q = np.zeros(max(K * n, 1), QUERY_DTYPE) if want_queries else None
+        bi, bd = np.empty(max(K * n, 1), np.int32), np.empty(max(K * n, 1), np.int32)
+        na = np.zeros(max(K, 1), np.int32)
+        check(self._L.orbhip_fuse_row(self._ctx.handle, src_row_key, _p(t), K, _p(sk), _p(ur), _p(q), _p(bi), _p(bd), _p(na)),
+              self._ctx.handle, "orbhip_fuse_row")
+        return (None if q is None else q[:K * n].reshape(K, n).copy()), bi[:K * n].reshape(K, n).copy(), bd[:K * n].reshape(K, n).copy(), na[:K].copy()
+
+    def fuse_collect(self, target, cur_row_key, kf_keys, cap, u_right=None, want_queries=True):
+        """The second pass: the ordered union of the rows kf_keys into the one target, whose own row is cur_row_key.  Returns
+        (keys, queries or None, best_idx, best_dist, n_active)."""
+        t = np.ascontiguousarray(target, FUSE_TARGET_DTYPE)
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, f32)
+        keys = np.zeros(max(cap, 1), np.uint64)
+        q = np.zeros(max(cap, 1), QUERY_DTYPE) if want_queries else None
+        bi, bd = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.int32)
+        nc, na = C.c_int(), C.c_int()
+        try:
+            check(self._L.orbhip_fuse_collect(self._ctx.handle, _p(t), cur_row_key, len(kk), _p(kk), _p(ur), _p(keys), cap, C.byref(nc),
+                                              _p(q), _p(bi), _p(bd), C.byref(na)), self._ctx.handle, "orbhip_fuse_collect")
+        except capi.OrbHipError as e:
+            e.partial, e.total = keys[:cap].copy(), nc.value
+            raise
+        m = nc.value
+        return keys[:m].copy(), (None if q is None else q[:m].copy()), bi[:m].copy(), bd[:m].copy(), na.value
 
     def search_last_frame_device(self, d_kps, d_desc, d_counts, cap, B, d_u_right, d_occupied, gp, d_cell_off, d_cell_idx, d_cam, d_slots,
                                  d_last_kps, d_motion, d_nq, cap_q, check_ori, th_high, d_queries, d_n_active, d_match, d_nmatches):

@@ -891,6 +891,56 @@ int orbhip_fuse_collect(orbhip_ctx *ctx, const orbhip_fuse_target *target, uint6
                         const float *u_right, uint64_t *keys_out, int cap, int *ncand, orbhip_proj_query *queries_out,
                         int32_t *best_idx, int32_t *best_dist, int32_t *n_active);
 
+/* ---- LoopClosing's two projection searches on the resident map ----
+ * LoopClosing::ComputeSim3 (ref: src/LoopClosing.cc:404-427) gathers the points of the matched key frame and its covisibles and calls
+ * SearchByProjection(mpCurrentKF, mScw, mvpLoopMapPoints, mvpCurrentMatchedPoints, 10) (ref: src/ORBmatcher.cc:290-403);
+ * LoopClosing::SearchAndFuse (ref: :647-673) calls Fuse(pKF, Scw, mvpLoopMapPoints, 4, vpReplacePoints) (ref: :977-1100) once per
+ * corrected key frame, each time with the whole list.  Everything both read is resident.
+ *   orbhip_fuse_sim3           the search half of Fuse(pKF, Scw, ...) (:977-1080) for K targets in one call;
+ *   orbhip_search_loop_points  orbhip_map_collect over kf_keys (= mvpLoopMapPoints element for element), the list projected from
+ *                              where it lies on the device and matched by the sequential claim of orbhip_search_by_projection;
+ *   orbhip_map_kf_set_batch    orbhip_map_kf_set for entries of many key frames: one upload, one launch, one synchronisation.
+ * targets [K] / target: cam holds Rcw, tcw, Ow as the reference's decomposition of Scw gives them (:986-990: Rcw = sRcw / s,
+ * tcw = t / s, Ow = -Rcw' tcw; the caller decomposes on the host), the target's intrinsics, bounds, scale tables and th; mbf,
+ * viewing_cos_limit, inv_level_sigma2 are not read and there is no u_right; level_ratio is filled by the call.  A set key may repeat.
+ * orbhip_fuse_sim3:
+ *   point_keys [n]      mvpLoopMapPoints as store keys; 0 = no point
+ *   target_row_keys [K] or NULL: the target's row in the key-frame table, 0 = none.  Point i is inactive for target k when the store
+ *                       does not know its key, when it is ORBHIP_MP_BAD, or when a live entry of row k resolves to its slot
+ *                       (spAlreadyFound = pKF->GetMapPoints(), :993, :1005; an entry resolves when its generation is the slot's and
+ *                       the point is not bad, so a stale entry whose slot went to another point of the list closes nothing)
+ *   queries_out [K][n] or NULL; best_idx, best_dist [K][n]; n_active [K]: per (target, point) what the loop of :1062-1079 finds, as
+ *                       orbhip_window_best_set defines them with inv_level_sigma2 == NULL (no chi-square gate; -1 / 256: inactive,
+ *                       or no feature closer than 256).  proj_xr of a query is 0.
+ *   Row k equals, bit for bit, the host projection followed by orbhip_window_best_set on the store as it stands at the call.
+ *   The projection is that of orbhip_fuse_row operation for operation (:1012-1049 is :850-888 line for line).
+ *   K == 0: ORBHIP_OK, nothing is written.  n == 0: n_active all 0, nothing is launched.
+ *   ORBHIP_E_ARG, with no output touched: no store; no table while a row key is non-zero; an unknown row or set; a target without a
+ *   grid; K < 0 or n < 0; more distinct set keys than the set limit in force; nlevels outside 1..16; a th that is not finite; a
+ *   non-zero key twice in point_keys.  ORBHIP_E_SIZE, likewise: K above 65535, K * n beyond 2^24, a target set of 2^20 features or more.
+ * orbhip_search_loop_points:
+ *   kf_keys [nkf], keys_out [cap], *npoints   as orbhip_map_collect.  ORBHIP_E_CAPACITY when *npoints exceeds cap: the first cap keys
+ *                       are filled, *npoints has the number, *n_active and *nmatches are 0 and match is all -1
+ *   matched_keys [size of target->set_key] or NULL: vpMatched as keys, 0 = NULL.  A feature with a non-zero entry is closed (:375); a
+ *                       point whose key occurs there is inactive (:306-317)
+ *   th_high             the bound on the best distance (:394; the drop-in passes TH_LOW)
+ *   queries_out [cap] or NULL (flags ORBHIP_Q_ACTIVE | ORBHIP_Q_OBSERVED); match [size of the set], *nmatches as
+ *                       orbhip_search_by_projection defines them with use_ratio = 0 and check_ori = 0; match[i] indexes keys_out
+ *   The result equals orbhip_search_by_projection fed with the host projection's queries.
+ *   ORBHIP_E_ARG / ORBHIP_E_SIZE with no output touched: those of orbhip_fuse_collect (it has no cur_row_key), and a target set too
+ *   large for the match table in LDS.  No key frames or only empty rows: counts 0, match all -1, nothing is launched.
+ * orbhip_map_kf_set_batch: kf_keys, idx, point_keys [m]; entry j sets index idx[j] of key frame kf_keys[j]'s row.  ORBHIP_E_ARG, the
+ *   table unchanged: an unknown key frame or point, an index outside its row, a point twice within one row after the edits, a
+ *   (key frame, index) pair twice in the call.  The table afterwards equals the table after orbhip_map_kf_set per key frame.
+ * Divergences from the reference, by design: as orbhip_fuse_row. */
+int orbhip_fuse_sim3(orbhip_ctx *ctx, const orbhip_fuse_target *targets, const uint64_t *target_row_keys, int K,
+                     const uint64_t *point_keys, int n, orbhip_proj_query *queries_out, int32_t *best_idx, int32_t *best_dist,
+                     int32_t *n_active);
+int orbhip_search_loop_points(orbhip_ctx *ctx, const orbhip_fuse_target *target, int nkf, const uint64_t *kf_keys,
+                              const uint64_t *matched_keys, int th_high, uint64_t *keys_out, int cap, int *npoints,
+                              orbhip_proj_query *queries_out, int *n_active, int32_t *match, int *nmatches);
+int orbhip_map_kf_set_batch(orbhip_ctx *ctx, int m, const uint64_t *kf_keys, const int32_t *idx, const uint64_t *point_keys);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

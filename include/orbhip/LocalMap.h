@@ -115,6 +115,31 @@ public:
     // Both bring the resident state up to date with every edit they make: the rows of the key frames a replaced point was
     // observed in, its flags, the survivor's descriptor and flags, the row entry and the flags of an added observation.
 
+    // ---- LoopClosing's two projection searches on the resident map (orbhip_search_loop_points, orbhip_fuse_sim3,
+    // orbhip_map_kf_set_batch) ----
+    // LoopClosing::ComputeSim3 from "Retrieve MapPoints seen in Loop Keyframe and neighbors" on (ref: src/LoopClosing.cc:404-427):
+    // vpLoopMapPoints is filled element for element from the rows of vpLoopConnectedKFs (in that order; bad points and second
+    // occurrences left out), projected with Scw into pCurrentKF and matched as ORBmatcher::SearchByProjection(pCurrentKF, Scw,
+    // vpLoopMapPoints, vpCurrentMatchedPoints, th) does (ref: src/ORBmatcher.cc:290-403): vpCurrentMatchedPoints gains the new
+    // matches, the return value is theirs.  The union never leaves the device except as the list itself.  The stamp
+    // mnLoopPointForKF is not written: nothing else reads it.
+    int SearchLoopPoints(KeyFrame *pCurrentKF, const cv::Mat &Scw, const std::vector<KeyFrame *> &vpLoopConnectedKFs,
+                         std::vector<MapPoint *> &vpLoopMapPoints, std::vector<MapPoint *> &vpCurrentMatchedPoints, int th);
+    // LoopClosing::SearchAndFuse (ref: src/LoopClosing.cc:647-673): matcher.Fuse(pKF, Scw, vpLoopMapPoints, th, vpReplacePoints)
+    // and the Replace loop behind it for every (key frame, corrected similarity) of vCorrectedPoses, in the vector's order (the
+    // reference walks a map<KeyFrame*, ...> by heap address; docs/parity.md).  All targets are projected and searched in one
+    // device call (64 at a time beyond that); the results are applied target by target, re-reading isBad(), GetMapPoints() and
+    // what the feature holds at that moment, and a loop point whose descriptor changed because it survived a Replace in an
+    // earlier target is searched again before a later target is applied.  Points that CorrectLoop moved must have been Put.
+    void SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::Mat> > &vCorrectedPoses, const std::vector<MapPoint *> &vpLoopMapPoints,
+                       float th = 4);
+    // where SearchAndFuse spends its time, in microseconds, summed over the calls since the caller last zeroed it
+    // (tools/loopfuse_latency.py): preparation, device call, second searches, apply and Replace loops, resident state
+    struct LoopPhases { double prepare, device, research, apply, resident; };
+    static LoopPhases &Phases() { static LoopPhases p = {0, 0, 0, 0, 0}; return p; }
+    // for the tests: without the second search of changed survivors the result differs from the reference's
+    static bool &ResearchChangedSurvivors() { static bool b = true; return b; }
+
     // device of the objects constructed from now on (default 0)
     static void SetDevice(int device);
 
@@ -132,6 +157,10 @@ protected:
     };
     int ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMPs, const int32_t *bestIdx, const int32_t *bestDist, FuseEdits &edits);
     bool FlushFuse(FuseEdits &edits);
+    typedef std::map<uint64_t, std::pair<std::vector<int32_t>, std::vector<uint64_t> > > FuseRows;
+    bool FlushFusePoints(FuseEdits &edits);                       // the store's half of FlushFuse
+    void FuseRowEdits(const FuseEdits &edits, FuseRows &rows);    // the table's half, as lists per key frame
+    bool FlushLoop(FuseEdits &edits);                             // FlushFuse with one orbhip_map_kf_set_batch (LocalMapLoop.cc)
     bool EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey);
 
     orbhip_ctx *mpCtx;
@@ -140,7 +169,7 @@ protected:
     std::map<uint64_t, KeyFrame *> mKeyFrameOf;
     bool mbKeyFrames = false;
     size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
-    size_t mnLastCandidates = 0;
+    size_t mnLastCandidates = 0, mnLastLoopPoints = 0;
     bool mbFuseSets = false;                   // the set limit has been raised for the targets of FuseInTargets
 };
 

@@ -6,44 +6,6 @@
 // allocated beyond the grow-only scratch of the context.
 #include "localmap_store.h"
 
-#define FUSE_MAX_QUERIES ((int64_t)1 << 24)   // K * n of one call
-#define FUSE_MAX_TARGETS 65535                // one target per blockIdx.y
-#define FUSE_MAX_SET (1 << 20)                // features of a target set: the row kernel keeps a position in 20 bits
-
-static bool fuse_camera_ok(const orbhip_local_camera *cam) { return cam->nlevels >= 1 && cam->nlevels <= 16 && std::isfinite(cam->th); }
-
-// the K target records of a call, the scratch for their grid-ordered feature records carved behind `recBase`
-struct FuseTargets {
-    std::vector<OrbSetView> view;
-    std::vector<size_t> recOff;   // bytes from the start of the record scratch
-    size_t recBytes = 0, urTotal = 0;
-    int maxN = 0;
-};
-
-static int fuse_targets_resolve(orbhip_ctx *c, const char *who, const orbhip_fuse_target *targets, int K, FuseTargets &T)
-{
-    std::vector<uint64_t> keys;
-    for (int k = 0; k < K; k++)
-        if (std::find(keys.begin(), keys.end(), targets[k].set_key) == keys.end()) keys.push_back(targets[k].set_key);
-    if ((int)keys.size() > orb_set_limit_in_force(c))
-        return fail(c, ORBHIP_E_ARG, std::string(who) + ": more distinct sets than the set limit in force (orbhip_set_limit)");
-    T.view.resize(K);
-    T.recOff.resize(K);
-    for (int k = 0; k < K; k++) {
-        if (!orb_set_grid_view(c, targets[k].set_key, &T.view[k]))
-            return fail(c, ORBHIP_E_ARG, std::string(who) + ": a target is an unknown set, or a set without a grid (orbhip_set_put)");
-        if (!fuse_camera_ok(&targets[k].cam)) return fail(c, ORBHIP_E_ARG, std::string(who) + ": nlevels outside 1..16, or th not finite");
-    }
-    for (int k = 0; k < K; k++) {
-        if (T.view[k].n >= FUSE_MAX_SET) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": a target set has 2^20 features or more");
-        T.recOff[k] = T.recBytes;
-        T.recBytes += align_up((size_t)T.view[k].n * 16, 256);
-        T.urTotal += (size_t)T.view[k].n;
-        T.maxN = std::max(T.maxN, T.view[k].n);
-    }
-    return ORBHIP_OK;
-}
-
 extern "C" int orbhip_fuse_row(orbhip_ctx *c, uint64_t src_row_key, const orbhip_fuse_target *targets, int K, const uint8_t *skip,
                                const float *u_right, orbhip_proj_query *queries_out, int32_t *best_idx, int32_t *best_dist,
                                int32_t *n_active)

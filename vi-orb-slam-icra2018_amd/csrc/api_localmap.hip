@@ -515,6 +515,25 @@ extern "C" int orbhip_map_kf_put(orbhip_ctx *c, uint64_t kf_key, int n, const ui
     return ORBHIP_OK;
 }
 
+// A point twice in the row `ent` as it will be, idx [m] being the entries that changed (a later entry of the call may have emptied
+// the index an earlier one filled: compare what stays).  One pass over the row against the sorted values of the changed indices: a
+// Fuse pass sets a hundred entries of a row at a time.
+static bool kf_row_twice(const std::vector<uint64_t> &ent, const int32_t *idx, int m)
+{
+    std::vector<uint8_t> touched(ent.size(), 0);
+    std::vector<uint64_t> vals;
+    for (int j = 0; j < m; j++) {
+        if (touched[idx[j]]) continue;
+        touched[idx[j]] = 1;
+        if (ent[idx[j]] != KF_NONE) vals.push_back(ent[idx[j]]);
+    }
+    std::sort(vals.begin(), vals.end());
+    bool twice = std::adjacent_find(vals.begin(), vals.end()) != vals.end();
+    for (size_t i = 0; i < ent.size() && !twice; i++)
+        twice = !touched[i] && ent[i] != KF_NONE && std::binary_search(vals.begin(), vals.end(), ent[i]);
+    return twice;
+}
+
 extern "C" int orbhip_map_kf_set(orbhip_ctx *c, uint64_t kf_key, int m, const int32_t *idx, const uint64_t *point_keys)
 {
     if (!c || kf_key == 0 || m < 0 || (m > 0 && (!idx || !point_keys))) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: bad argument");
@@ -530,22 +549,7 @@ extern "C" int orbhip_map_kf_set(orbhip_ctx *c, uint64_t kf_key, int m, const in
         if (idx[j] < 0 || idx[j] >= (int)ent.size()) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: an index outside the row");
         if (!kf_resolve(M, point_keys[j], &ent[idx[j]])) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point key is not in the store");
     }
-    {   // a point twice in the row as it will be (a later entry of the call may have emptied the index an earlier one filled:
-        // compare what stays).  One pass over the row against the sorted values of the changed indices: a Fuse pass sets a
-        // hundred entries of a row at a time.
-        std::vector<uint8_t> touched(ent.size(), 0);
-        std::vector<uint64_t> vals;
-        for (int j = 0; j < m; j++) {
-            if (touched[idx[j]]) continue;
-            touched[idx[j]] = 1;
-            if (ent[idx[j]] != KF_NONE) vals.push_back(ent[idx[j]]);
-        }
-        std::sort(vals.begin(), vals.end());
-        bool twice = std::adjacent_find(vals.begin(), vals.end()) != vals.end();
-        for (size_t i = 0; i < ent.size() && !twice; i++)
-            twice = !touched[i] && ent[i] != KF_NONE && std::binary_search(vals.begin(), vals.end(), ent[i]);
-        if (twice) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point appears twice in the row");
-    }
+    if (kf_row_twice(ent, idx, m)) return fail(c, ORBHIP_E_ARG, "orbhip_map_kf_set: a point appears twice in the row");
     HIPCHK(c, orb_enter(c));
     Packed P(c);
     int rc;
@@ -563,6 +567,63 @@ extern "C" int orbhip_map_kf_set(orbhip_ctx *c, uint64_t kf_key, int m, const in
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
     K->entries[row].swap(ent);
+    return ORBHIP_OK;
+}
+
+// orbhip_map_kf_set for entries of many key frames: one upload, one launch, one synchronisation
+extern "C" int orbhip_map_kf_set_batch(orbhip_ctx *c, int m, const uint64_t *kf_keys, const int32_t *idx, const uint64_t *point_keys)
+{
+    const char *who = "orbhip_map_kf_set_batch";
+    if (!c || m < 0 || (m > 0 && (!kf_keys || !idx || !point_keys))) return fail(c, ORBHIP_E_ARG, std::string(who) + ": bad argument");
+    OrbLocalMap *M = lmap(c);
+    OrbKfTable *K = kf_table(c);
+    if (!K) return fail(c, ORBHIP_E_ARG, std::string(who) + ": no table (orbhip_map_kf_init)");
+    if (m == 0) return ORBHIP_OK;
+    // the entries of each row, in the order of the call
+    std::vector<int32_t> rows;                                  // the rows of the call, in order of first appearance
+    std::unordered_map<int32_t, std::vector<int32_t> > of;      // row -> the positions j of the call that name it
+    for (int j = 0; j < m; j++) {
+        auto it = kf_keys[j] ? K->rowOf.find(kf_keys[j]) : K->rowOf.end();
+        if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": unknown key frame");
+        std::vector<int32_t> &v = of[it->second];
+        if (v.empty()) rows.push_back(it->second);
+        v.push_back(j);
+    }
+    std::vector<std::vector<uint64_t> > after(rows.size());     // the rows as they will be
+    std::vector<int32_t> ridx;
+    for (size_t r = 0; r < rows.size(); r++) {
+        std::vector<uint64_t> &ent = after[r];
+        ent = K->entries[rows[r]];
+        const std::vector<int32_t> &js = of[rows[r]];
+        std::vector<uint8_t> named(ent.size(), 0);
+        ridx.clear();
+        for (int32_t j : js) {
+            if (idx[j] < 0 || idx[j] >= (int)ent.size()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": an index outside the row");
+            if (named[idx[j]]) return fail(c, ORBHIP_E_ARG, std::string(who) + ": a (key frame, index) pair twice in the call");
+            named[idx[j]] = 1;
+            if (!kf_resolve(M, point_keys[j], &ent[idx[j]])) return fail(c, ORBHIP_E_ARG, std::string(who) + ": a point key is not in the store");
+            ridx.push_back(idx[j]);
+        }
+        if (kf_row_twice(ent, ridx.data(), (int)ridx.size())) return fail(c, ORBHIP_E_ARG, std::string(who) + ": a point appears twice in a row");
+    }
+    HIPCHK(c, orb_enter(c));
+    Packed P(c);
+    int rc;
+    if ((rc = P.begin((size_t)m * 16 + 2 * 256))) return rc;
+    int64_t *hat;
+    int32_t *hval;
+    const int64_t *dat = (const int64_t *)P.in_reserve((size_t)m * 8, (void **)&hat);
+    const void *dval = P.in_reserve((size_t)m * 8, (void **)&hval);
+    for (size_t r = 0; r < rows.size(); r++)
+        for (int32_t j : of[rows[r]]) {
+            hat[j] = (int64_t)rows[r] * K->stride + 1 + idx[j];
+            kf_unpack(after[r][idx[j]], hval + 2 * j);
+        }
+    if ((rc = P.upload())) return rc;
+    launch_kf_set(c->stream, dat, dval, m, (int64_t)K->maxKfs * K->stride, K->rows.as<void>());
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t r = 0; r < rows.size(); r++) K->entries[rows[r]].swap(after[r]);
     return ORBHIP_OK;
 }
 

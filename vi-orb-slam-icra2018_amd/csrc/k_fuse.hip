@@ -3,13 +3,14 @@
 //   k_project_fuse       the projection loop (:842-890).  One lane per (target, source entry), blockIdx.y = the target, whose
 //                        camera record therefore arrives through scalar loads.  ROW: the source is a row of the key-frame table
 //                        (an entry resolves through kf_entry_slot: live, not bad, the entry's generation); otherwise it is the
-//                        slot list an ordered union left on the device, `*nq` long.  The point is gathered from the store's
-//                        structure of arrays by slot (whole dwordx4 loads).  Writes one query per entry -- all zero when
-//                        inactive -- and the slot array of the search, and counts the active queries per target.
+//                        slot list an ordered union left on the device, `*nq` long, the same list for every target.  SIM3: the
+//                        cameras are decomposed similarities (Fuse(pKF, Scw, ...), ref: :977-1049), proj_xr is 0.  The point is
+//                        gathered from the store's structure of arrays by slot (whole dwordx4 loads).  Writes one query per entry
+//                        -- all zero when inactive -- and the slot array of the search, and counts the active queries per target.
 //   k_fuse_records       the grid-ordered feature records {x, y, octave | index << 8} of all K target sets in one launch
 //   k_window_best_sets   the window search of k_window_best_row (k_guided.hip; the same inner loop, window_row_best) with a
-//                        per-target record selected by blockIdx.y, the chi-square gate always on and the query's descriptor read
-//                        from the store by slot.
+//                        per-target record selected by blockIdx.y, the chi-square gate on (Fuse) or off (Fuse with a similarity,
+//                        DESIGN.md section 18) and the query's descriptor read from the store by slot.
 // The arithmetic of k_project_fuse is that of Fuse, operation for operation, not that of the frame searches (k_projtrack.hip):
 // the camera point is one gemm (double sums, one rounding); invz = 1 / z is a FLOAT division (the host path's kf_window divides in
 // double and rounds: the two agree for every float, docs/parity.md); x = xc * invz and then u = fx * x + cx, each operation rounded
@@ -35,7 +36,7 @@ struct FuseTargetDev {
     float invSigma2[16];
 };
 
-template <bool ROW>
+template <bool ROW, bool SIM3>
 __global__ __launch_bounds__(256) void k_project_fuse(const float4 *__restrict__ geoA, const float4 *__restrict__ geoB,
                                                       const uint32_t *__restrict__ mflags, int maxPoints,
                                                       const uint32_t *__restrict__ marks, const int2 *__restrict__ row, int rowCap,
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(256) void k_project_fuse(const float4 *__restrict__
                 const float u = __fadd_rn(__fmul_rn(C.fx, x), C.cx);       // :861-862
                 const float v = __fadd_rn(__fmul_rn(C.fy, y), C.cy);
                 if (!(u >= C.min_x && u < C.max_x && v >= C.min_y && v < C.max_y)) break;   // :865, src/KeyFrame.cc IsInImage
-                const float ur = __fsub_rn(u, __fmul_rn(C.mbf, invz));     // :868
+                const float ur = SIM3 ? 0.0f : __fsub_rn(u, __fmul_rn(C.mbf, invz));   // :868; Fuse(pKF, Scw, ...) has none
                 const float ox = __fsub_rn(A.x, C.Ow[0]), oy = __fsub_rn(A.y, C.Ow[1]), oz = __fsub_rn(A.z, C.Ow[2]);   // :872
                 double sq = __dadd_rn(0.0, __dmul_rn((double)ox, (double)ox));
                 sq = __dadd_rn(sq, __dmul_rn((double)oy, (double)oy));
@@ -120,7 +121,9 @@ __global__ __launch_bounds__(256) void k_fuse_records(const FuseTargetDev *__res
     T.rec[j] = make_float4(k.x, k.y, __int_as_float((k.octave & 255) | (idx << 8)), 0.f);
 }
 
-// queries, qslot, bestIdx, bestDist [K][capQ]; an inactive query never reads its slot
+// queries, qslot, bestIdx, bestDist [K][capQ]; an inactive query never reads its slot.  GATE = false: the loop of Fuse(pKF, Scw, ...)
+// (ref: src/ORBmatcher.cc:1062-1079), which has no chi-square test; uRight and invSigma2 are not read then.
+template <bool GATE>
 __global__ __launch_bounds__(256) void k_window_best_sets(const FuseTargetDev *__restrict__ targets,
                                                           const orbhip_proj_query *__restrict__ queries,
                                                           const uint4 *__restrict__ mdesc, const int32_t *__restrict__ qslot, int capQ,
@@ -138,7 +141,7 @@ __global__ __launch_bounds__(256) void k_window_best_sets(const FuseTargetDev *_
     if ((q.flags & ORBHIP_Q_ACTIVE) && window_cells(T.gp, q.u, q.v, q.radius, x0, x1, y0, y1)) {
         const uint4 *qd = mdesc + 2 * (size_t)qslot[at];
         const float *sig = T.invSigma2;
-        window_row_best(q, x0, x1, y0, y1, qd[0], qd[1], T.desc, T.uRight, T.rec, T.cellOff, true,
+        window_row_best(q, x0, x1, y0, y1, qd[0], qd[1], T.desc, T.uRight, T.rec, T.cellOff, GATE,
                         [sig](int oct) { return sig[oct & 15]; }, s_start[row], s_excl[row], gl, key, myIdx);
     }
     window_row_store(key, myIdx, gl, bestIdx + at, bestDist + at);
@@ -149,7 +152,7 @@ void launch_project_fuse_row(hipStream_t s, const void *geoA, const void *geoB, 
                              int rowCap, const uint8_t *skip, const orbhip_local_camera *cams, int capQ, int K,
                              orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive)
 {
-    hipLaunchKernelGGL(k_project_fuse<true>, dim3((capQ + 255) / 256, K, 1), dim3(256, 1, 1), 0, s, (const float4 *)geoA,
+    hipLaunchKernelGGL((k_project_fuse<true, false>), dim3((capQ + 255) / 256, K, 1), dim3(256, 1, 1), 0, s, (const float4 *)geoA,
                        (const float4 *)geoB, mflags, maxPoints, (const uint32_t *)nullptr, (const int2 *)row, rowCap,
                        (const int32_t *)nullptr, (const int32_t *)nullptr, skip, cams, capQ, queries, slotsOut, nActive);
 }
@@ -159,7 +162,7 @@ void launch_project_fuse_list(hipStream_t s, const void *geoA, const void *geoB,
                               const uint32_t *marks, const int32_t *slots, const int32_t *nq, const orbhip_local_camera *cam, int capQ,
                               orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive)
 {
-    hipLaunchKernelGGL(k_project_fuse<false>, dim3((capQ + 255) / 256, 1, 1), dim3(256, 1, 1), 0, s, (const float4 *)geoA,
+    hipLaunchKernelGGL((k_project_fuse<false, false>), dim3((capQ + 255) / 256, 1, 1), dim3(256, 1, 1), 0, s, (const float4 *)geoA,
                        (const float4 *)geoB, mflags, maxPoints, marks, (const int2 *)nullptr, 0, slots, nq, (const uint8_t *)nullptr, cam,
                        capQ, queries, slotsOut, nActive);
 }
@@ -181,11 +184,28 @@ void fuse_target_fill(void *dst, const void *kps, const void *desc, const int32_
     memcpy(dst, &t, sizeof t);
 }
 
+// the list form for K targets that each carry their own similarity (Fuse(pKF, Scw, ...), ref: :977-1049; SearchByProjection(pKF,
+// Scw, ...), :290-360): the same list for every target, skip [K][capQ] or null, marks or null; proj_xr is written as 0
+void launch_project_fuse_sim3(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
+                              const uint32_t *marks, const int32_t *slots, const int32_t *nq, const uint8_t *skip,
+                              const orbhip_local_camera *cams, int capQ, int K, orbhip_proj_query *queries, int32_t *slotsOut,
+                              int32_t *nActive)
+{
+    hipLaunchKernelGGL((k_project_fuse<false, true>), dim3((capQ + 255) / 256, K, 1), dim3(256, 1, 1), 0, s, (const float4 *)geoA,
+                       (const float4 *)geoB, mflags, maxPoints, marks, (const int2 *)nullptr, 0, slots, nq, skip, cams, capQ, queries,
+                       slotsOut, nActive);
+}
+
 // targets [K] (device); maxN = the largest set among them
 void launch_window_best_sets(hipStream_t s, const void *targets, int K, int maxN, const orbhip_proj_query *queries, const void *mdesc,
-                             const int32_t *qslot, int capQ, int32_t *bestIdx, int32_t *bestDist)
+                             const int32_t *qslot, int capQ, int32_t *bestIdx, int32_t *bestDist, bool gate)
 {
     hipLaunchKernelGGL(k_fuse_records, dim3((maxN + 255) / 256, K, 1), dim3(256, 1, 1), 0, s, (const FuseTargetDev *)targets);
-    hipLaunchKernelGGL(k_window_best_sets, dim3((capQ + 15) / 16, K, 1), dim3(256, 1, 1), 0, s, (const FuseTargetDev *)targets, queries,
-                       (const uint4 *)mdesc, qslot, capQ, bestIdx, bestDist);
+    const dim3 grid((capQ + 15) / 16, K, 1), block(256, 1, 1);
+    if (gate)
+        hipLaunchKernelGGL(k_window_best_sets<true>, grid, block, 0, s, (const FuseTargetDev *)targets, queries, (const uint4 *)mdesc, qslot,
+                           capQ, bestIdx, bestDist);
+    else
+        hipLaunchKernelGGL(k_window_best_sets<false>, grid, block, 0, s, (const FuseTargetDev *)targets, queries, (const uint4 *)mdesc, qslot,
+                           capQ, bestIdx, bestDist);
 }

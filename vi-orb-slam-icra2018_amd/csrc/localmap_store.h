@@ -1,6 +1,6 @@
 // localmap_store.h -- the host side of the resident map-point store and of the key-frame table, shared by the api_*.hip files
-// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip): device blocks, the key -> slot / key -> row tables and
-// what a call over several rows of the table (the ordered union) sets up.
+// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip): device blocks, the key -> slot / key -> row
+// tables, what a call over several rows of the table (the ordered union) sets up, and the target records of the Fuse calls.
 #ifndef ORBHIP_LOCALMAP_STORE_H
 #define ORBHIP_LOCALMAP_STORE_H
 #include "api_common.h"
@@ -94,6 +94,45 @@ static inline int kf_call_scratch(orbhip_ctx *c, OrbKfTable *K, KfCall &Q, int c
     Q.d_cand = K->scratch.as<int32_t>();
     Q.d_blockCnt = (int32_t *)(K->scratch.as<uint8_t>() + candBytes);
     Q.d_skip = K->scratch.as<uint8_t>() + candBytes + cntBytes;
+    return ORBHIP_OK;
+}
+
+// ---- the K target key frames of a Fuse call (api_fuse.hip, api_loopfuse.hip) ----
+#define FUSE_MAX_QUERIES ((int64_t)1 << 24)   // K * n of one call
+#define FUSE_MAX_TARGETS 65535                // one target per blockIdx.y
+#define FUSE_MAX_SET (1 << 20)                // features of a target set: the row kernel keeps a position in 20 bits
+
+static inline bool fuse_camera_ok(const orbhip_local_camera *cam) { return cam->nlevels >= 1 && cam->nlevels <= 16 && std::isfinite(cam->th); }
+
+// the K target records of a call, the scratch for their grid-ordered feature records carved behind `recBase`
+struct FuseTargets {
+    std::vector<OrbSetView> view;
+    std::vector<size_t> recOff;   // bytes from the start of the record scratch
+    size_t recBytes = 0, urTotal = 0;
+    int maxN = 0;
+};
+
+static inline int fuse_targets_resolve(orbhip_ctx *c, const char *who, const orbhip_fuse_target *targets, int K, FuseTargets &T)
+{
+    std::vector<uint64_t> keys;
+    for (int k = 0; k < K; k++)
+        if (std::find(keys.begin(), keys.end(), targets[k].set_key) == keys.end()) keys.push_back(targets[k].set_key);
+    if ((int)keys.size() > orb_set_limit_in_force(c))
+        return fail(c, ORBHIP_E_ARG, std::string(who) + ": more distinct sets than the set limit in force (orbhip_set_limit)");
+    T.view.resize(K);
+    T.recOff.resize(K);
+    for (int k = 0; k < K; k++) {
+        if (!orb_set_grid_view(c, targets[k].set_key, &T.view[k]))
+            return fail(c, ORBHIP_E_ARG, std::string(who) + ": a target is an unknown set, or a set without a grid (orbhip_set_put)");
+        if (!fuse_camera_ok(&targets[k].cam)) return fail(c, ORBHIP_E_ARG, std::string(who) + ": nlevels outside 1..16, or th not finite");
+    }
+    for (int k = 0; k < K; k++) {
+        if (T.view[k].n >= FUSE_MAX_SET) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": a target set has 2^20 features or more");
+        T.recOff[k] = T.recBytes;
+        T.recBytes += align_up((size_t)T.view[k].n * 16, 256);
+        T.urTotal += (size_t)T.view[k].n;
+        T.maxN = std::max(T.maxN, T.view[k].n);
+    }
     return ORBHIP_OK;
 }
 

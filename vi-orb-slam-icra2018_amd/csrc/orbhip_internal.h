@@ -545,7 +545,14 @@ size_t fuse_target_bytes();   // one per-target record of the search, written by
 void fuse_target_fill(void *dst, const void *kps, const void *desc, const int32_t *cellOff, const int32_t *cellIdx, void *rec,
                       const float *uRight, float minX, float minY, float invW, float invH, int n, const float *invSigma2);
 void launch_window_best_sets(hipStream_t s, const void *targets, int K, int maxN, const orbhip_proj_query *queries, const void *mdesc,
-                             const int32_t *qslot, int capQ, int32_t *bestIdx, int32_t *bestDist);
+                             const int32_t *qslot, int capQ, int32_t *bestIdx, int32_t *bestDist, bool gate = true);
+void launch_project_fuse_sim3(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
+                              const uint32_t *marks, const int32_t *slots, const int32_t *nq, const uint8_t *skip,
+                              const orbhip_local_camera *cams, int capQ, int K, orbhip_proj_query *queries, int32_t *slotsOut,
+                              int32_t *nActive);
+// k_loopfuse.hip
+void launch_loop_held(hipStream_t s, const void *rows, int stride, int maxRow, const int32_t *rowIdx, int K, int maxLen,
+                      const uint32_t *mflags, int maxPoints, uint32_t *marks, const int32_t *slots, int n, uint8_t *skip);
 // k_localcollect.hip
 void launch_mark_add(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
 void launch_mark_clear(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);

@@ -4,6 +4,7 @@
 #ifndef ORBHIP_HOST_MATCHERDETAIL_H
 #define ORBHIP_HOST_MATCHERDETAIL_H
 
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -73,6 +74,27 @@ inline void affine3(const cv::Mat &R, const float x[3], const float t[3], float 
         for (int k = 0; k < 3; k++) s += (double)(transpose ? R.at<float>(k, r) : R.at<float>(r, k)) * (double)x[k];
         out[r] = (float)(alpha * s + (t ? (double)t[r] : 0.0));
     }
+}
+
+// out = float(alpha * R) (or R transposed): what OpenCV materialises for s*R, R/s and (1/s)*R.t()
+inline void scale3(const cv::Mat &R, double alpha, bool transpose, cv::Mat &out)
+{
+    out = cv::Mat(3, 3, CV_32F);
+    for (int r = 0; r < 3; r++)
+        for (int k = 0; k < 3; k++)
+            out.at<float>(r, k) = (float)(alpha * (double)(transpose ? R.at<float>(k, r) : R.at<float>(r, k)));
+}
+
+// Scw -> Rcw, tcw, Ow (ref: :299-303, :989-993)
+inline void decompose_sim3(const cv::Mat &Scw, cv::Mat &Rcw, float tcw[3], float Ow[3])
+{
+    double dot = 0;
+    for (int k = 0; k < 3; k++) dot += (double)Scw.at<float>(0, k) * (double)Scw.at<float>(0, k);
+    const float scw = std::sqrt(dot);
+    const cv::Mat sRcw = Scw.rowRange(0,3).colRange(0,3);
+    scale3(sRcw, 1.0 / scw, false, Rcw);
+    for (int r = 0; r < 3; r++) tcw[r] = (float)((double)Scw.at<float>(r, 3) * (1.0 / scw));
+    affine3(Rcw, tcw, NULL, Ow, true, -1.0);                   // Ow = -Rcw.t()*tcw
 }
 
 // Epipole of key frame 1 in the image of key frame 2 (ref: src/ORBmatcher.cc:664-671): C2 = R2w*Cw+t2w projected

@@ -50,7 +50,9 @@ thread_local ThreadCtx tls;
 using hipdetail::Csr;
 using hipdetail::affine3;
 using hipdetail::contiguous;
+using hipdetail::decompose_sim3;
 using hipdetail::flatten;
+using hipdetail::scale3;
 
 // Resident feature sets (include/orbhip.h, orbhip_set_*): descriptors, undistorted keypoints, FeatureVector and feature grid of
 // a key frame or frame stay on the device under its id once a matcher of this thread has met it (a set nobody uses any
@@ -388,26 +390,7 @@ namespace {
 // The wrappers project the points on the host exactly as the reference's loops do (cv::gemm arithmetic: double
 // accumulation, one rounding), hand the windows to the device and apply the map updates in the reference's order.
 
-// out = float(alpha * R) (or R transposed): what OpenCV materialises for s*R, R/s and (1/s)*R.t()
-void scale3(const cv::Mat &R, double alpha, bool transpose, cv::Mat &out)
-{
-    out = cv::Mat(3, 3, CV_32F);
-    for (int r = 0; r < 3; r++)
-        for (int k = 0; k < 3; k++)
-            out.at<float>(r, k) = (float)(alpha * (double)(transpose ? R.at<float>(k, r) : R.at<float>(r, k)));
-}
-
-// Scw -> Rcw, tcw, Ow (ref: :299-303, :989-993)
-void decompose_sim3(const cv::Mat &Scw, cv::Mat &Rcw, float tcw[3], float Ow[3])
-{
-    double dot = 0;
-    for (int k = 0; k < 3; k++) dot += (double)Scw.at<float>(0, k) * (double)Scw.at<float>(0, k);
-    const float scw = sqrt(dot);
-    const cv::Mat sRcw = Scw.rowRange(0,3).colRange(0,3);
-    scale3(sRcw, 1.0 / scw, false, Rcw);
-    for (int r = 0; r < 3; r++) tcw[r] = (float)((double)Scw.at<float>(r, 3) * (1.0 / scw));
-    affine3(Rcw, tcw, NULL, Ow, true, -1.0);                   // Ow = -Rcw.t()*tcw
-}
+// (scale3 and decompose_sim3, which LoopClosing's searches on the resident map share: MatcherDetail.h)
 
 inline float norm3(const float a[3])                           // cv::norm of a float vector sums the squares in double
 {

@@ -1,4 +1,4 @@
-// LocalMapDetail.h -- what LocalMap.cc, LocalMapCollect.cc, LocalMapProjTrack.cc and LocalMapFuse.cc share: keys and flags of a MapPoint, the frame as a resident
+// LocalMapDetail.h -- what LocalMap.cc, LocalMapCollect.cc, LocalMapProjTrack.cc, LocalMapFuse.cc and LocalMapLoop.cc share: keys and flags of a MapPoint, the frame as a resident
 // set, the camera block of a search and the write-back of its results (ref: src/Tracking.cc:2336-2364, src/Frame.cc:613-669,
 // src/ORBmatcher.cc:45-129).
 #ifndef ORBHIP_LOCALMAP_DETAIL_H
@@ -87,6 +87,35 @@ inline void write_back(Frame &F, const std::vector<MapPoint *> &vpLocalMapPoints
     }
     for (int i = 0; i < n; i++)
         if (match[i] >= 0 && match[i] < nq) F.mvpMapPoints[i] = vpLocalMapPoints[match[i]];   // ref: src/ORBmatcher.cc:123
+}
+// ---- the target key frames of the Fuse calls (LocalMapFuse.cc, LocalMapLoop.cc) ----
+inline bool has_pyramid(KeyFrame *pKF)
+{
+    return pKF->mnScaleLevels >= 1 && pKF->mnScaleLevels <= 16 && (int)pKF->mvScaleFactors.size() >= pKF->mnScaleLevels &&
+           (int)pKF->mvInvLevelSigma2.size() >= pKF->mnScaleLevels;
+}
+
+// the target key frame as Fuse reads it (ref: src/ORBmatcher.cc:827-838)
+inline void fill_target(KeyFrame *pKF, uint64_t setKey, float th, orbhip_fuse_target *out)
+{
+    memset(out, 0, sizeof *out);
+    out->set_key = setKey;
+    orbhip_local_camera &cam = out->cam;
+    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) cam.Rcw[3 * r + c] = R.at<float>(r, c);
+        cam.tcw[r] = t.at<float>(r, 0);
+        cam.Ow[r] = O.at<float>(r, 0);
+    }
+    cam.fx = pKF->fx, cam.fy = pKF->fy, cam.cx = pKF->cx, cam.cy = pKF->cy, cam.mbf = pKF->mbf;
+    cam.min_x = pKF->mnMinX, cam.max_x = pKF->mnMaxX, cam.min_y = pKF->mnMinY, cam.max_y = pKF->mnMaxY;
+    for (int l = 0; l < pKF->mnScaleLevels; l++) {
+        cam.scale_factors[l] = pKF->mvScaleFactors[l];
+        out->inv_level_sigma2[l] = pKF->mvInvLevelSigma2[l];
+    }
+    cam.log_scale_factor = pKF->mfLogScaleFactor;
+    cam.nlevels = pKF->mnScaleLevels;
+    cam.th = th;
 }
 }  // namespace localmapdetail
 }  // namespace ORB_SLAM2

@@ -12,7 +12,9 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::fill_target;
 using localmapdetail::flags_of;
+using localmapdetail::has_pyramid;
 using localmapdetail::key_of;
 using localmapdetail::set_key_of;
 
@@ -22,35 +24,6 @@ const uint64_t SNAPSHOT_ROW = 1ull << 61;   // the source list as it was when Fu
 const int FUSE_CHUNK = 64;                  // targets per device call: their sets stay resident beside the frames being tracked
 const int FUSE_SETS = 96;                   // the set limit from the first FuseInTargets on
 const int TH_LOW = 50;                      // ORBmatcher::TH_LOW
-
-bool has_pyramid(KeyFrame *pKF)
-{
-    return pKF->mnScaleLevels >= 1 && pKF->mnScaleLevels <= 16 && (int)pKF->mvScaleFactors.size() >= pKF->mnScaleLevels &&
-           (int)pKF->mvInvLevelSigma2.size() >= pKF->mnScaleLevels;
-}
-
-// the target key frame as Fuse reads it (ref: src/ORBmatcher.cc:827-838)
-void fill_target(KeyFrame *pKF, uint64_t setKey, float th, orbhip_fuse_target *out)
-{
-    memset(out, 0, sizeof *out);
-    out->set_key = setKey;
-    orbhip_local_camera &cam = out->cam;
-    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) cam.Rcw[3 * r + c] = R.at<float>(r, c);
-        cam.tcw[r] = t.at<float>(r, 0);
-        cam.Ow[r] = O.at<float>(r, 0);
-    }
-    cam.fx = pKF->fx, cam.fy = pKF->fy, cam.cx = pKF->cx, cam.cy = pKF->cy, cam.mbf = pKF->mbf;
-    cam.min_x = pKF->mnMinX, cam.max_x = pKF->mnMaxX, cam.min_y = pKF->mnMinY, cam.max_y = pKF->mnMaxY;
-    for (int l = 0; l < pKF->mnScaleLevels; l++) {
-        cam.scale_factors[l] = pKF->mvScaleFactors[l];
-        out->inv_level_sigma2[l] = pKF->mvInvLevelSigma2[l];
-    }
-    cam.log_scale_factor = pKF->mfLogScaleFactor;
-    cam.nlevels = pKF->mnScaleLevels;
-    cam.th = th;
-}
 
 bool is_stereo(KeyFrame *pKF) { return !pKF->mvKeysUn.empty() && pKF->mvuRight.size() == pKF->mvKeysUn.size(); }
 }  // namespace
@@ -104,8 +77,8 @@ int LocalMapSearch::ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMP
     return fused;
 }
 
-// the store and the table as the objects are now
-bool LocalMapSearch::FlushFuse(FuseEdits &edits)
+// the store as the objects are now: survivors' descriptors and flags, the flags of every other point an edit touched
+bool LocalMapSearch::FlushFusePoints(FuseEdits &edits)
 {
     bool ok = true;
     if (!edits.put.empty()) ok = PutLocked(std::vector<MapPoint *>(edits.put.begin(), edits.put.end())) && ok;
@@ -120,7 +93,12 @@ bool LocalMapSearch::FlushFuse(FuseEdits &edits)
         hipdetail::Fail("LocalMapSearch::Fuse (orbhip_map_update_flags)", orbhip_last_error(mpCtx));
         ok = false;
     }
-    std::map<uint64_t, std::pair<std::vector<int32_t>, std::vector<uint64_t> > > rows;
+    return ok;
+}
+
+// the row entries an edit may have changed, as the objects hold them now: key frame -> (indices, point keys)
+void LocalMapSearch::FuseRowEdits(const FuseEdits &edits, FuseRows &rows)
+{
     for (std::set<std::pair<KeyFrame *, size_t> >::const_iterator it = edits.entries.begin(); it != edits.entries.end(); ++it) {
         KeyFrame *kf = it->first;
         if (!mKeyFrameOf.count(key_of(kf))) continue;
@@ -129,7 +107,15 @@ bool LocalMapSearch::FlushFuse(FuseEdits &edits)
         rows[key_of(kf)].first.push_back((int32_t)it->second);
         rows[key_of(kf)].second.push_back(named ? key_of(p) : 0);
     }
-    for (std::map<uint64_t, std::pair<std::vector<int32_t>, std::vector<uint64_t> > >::const_iterator it = rows.begin(); it != rows.end(); ++it)
+}
+
+// the store and the table as the objects are now
+bool LocalMapSearch::FlushFuse(FuseEdits &edits)
+{
+    bool ok = FlushFusePoints(edits);
+    FuseRows rows;
+    FuseRowEdits(edits, rows);
+    for (FuseRows::const_iterator it = rows.begin(); it != rows.end(); ++it)
         if (orbhip_map_kf_set(mpCtx, it->first, (int)it->second.first.size(), it->second.first.data(), it->second.second.data()) != ORBHIP_OK) {
             hipdetail::Fail("LocalMapSearch::Fuse (orbhip_map_kf_set)", orbhip_last_error(mpCtx));
             ok = false;

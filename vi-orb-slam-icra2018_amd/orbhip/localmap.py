@@ -253,6 +253,53 @@ class LocalMap:
         m = nc.value
         return keys[:m].copy(), (None if q is None else q[:m].copy()), bi[:m].copy(), bd[:m].copy(), na.value
 
+    # ---- LoopClosing's projection searches on the resident map ----
+    def kf_set_batch(self, kf_keys, idx, point_keys):
+        """kf_set for entries of many key frames in one call: entry j sets index idx[j] of key frame kf_keys[j]'s row."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64).ravel()
+        idx, pk = np.ascontiguousarray(idx, np.int32).ravel(), np.ascontiguousarray(point_keys, np.uint64).ravel()
+        assert len(kk) == len(idx) == len(pk)
+        check(self._L.orbhip_map_kf_set_batch(self._ctx.handle, len(kk), _p(kk), _p(idx), _p(pk)), self._ctx.handle,
+              "orbhip_map_kf_set_batch")
+
+    def fuse_sim3(self, targets, target_row_keys, point_keys, want_queries=True):
+        """Fuse(pKF, Scw, vpPoints, th, ...) up to the map edits, for K targets (fuse_target records whose cam holds the decomposed
+        similarity) in one call.  target_row_keys: [K] (0: none) or None.  Returns (queries [K][n] or None, best_idx, best_dist,
+        n_active [K])."""
+        t = np.ascontiguousarray(targets, FUSE_TARGET_DTYPE)
+        pk = np.ascontiguousarray(point_keys, np.uint64).ravel()
+        K, n = len(t), len(pk)
+        rk = None if target_row_keys is None else np.ascontiguousarray(target_row_keys, np.uint64).ravel()
+        assert rk is None or len(rk) == K
+        q = np.zeros(max(K * n, 1), QUERY_DTYPE) if want_queries else None
+        bi, bd = np.empty(max(K * n, 1), np.int32), np.empty(max(K * n, 1), np.int32)
+        na = np.zeros(max(K, 1), np.int32)
+        check(self._L.orbhip_fuse_sim3(self._ctx.handle, _p(t), _p(rk), K, _p(pk), n, _p(q), _p(bi), _p(bd), _p(na)), self._ctx.handle,
+              "orbhip_fuse_sim3")
+        return (None if q is None else q[:K * n].reshape(K, n).copy()), bi[:K * n].reshape(K, n).copy(), bd[:K * n].reshape(K, n).copy(), na[:K].copy()
+
+    def search_loop_points(self, target, n, kf_keys, matched_keys, cap, th_high=50, want_queries=True):
+        """ComputeSim3's union of the rows kf_keys and SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) over it; n = the size of
+        the target's set, matched_keys: [n] (0: NULL) or None.  Returns (keys, queries or None, n_active, nmatches, match [n]
+        indexing keys)."""
+        t = np.ascontiguousarray(target, FUSE_TARGET_DTYPE)
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        mk = None if matched_keys is None else np.ascontiguousarray(matched_keys, np.uint64).ravel()
+        assert mk is None or len(mk) == n
+        keys = np.zeros(max(cap, 1), np.uint64)
+        q = np.zeros(max(cap, 1), QUERY_DTYPE) if want_queries else None
+        match = np.empty(max(n, 1), np.int32)
+        npts, na, nm = C.c_int(), C.c_int(), C.c_int()
+        try:
+            check(self._L.orbhip_search_loop_points(self._ctx.handle, _p(t), len(kk), _p(kk), _p(mk), th_high, _p(keys), cap, C.byref(npts),
+                                                    _p(q), C.byref(na), _p(match), C.byref(nm)), self._ctx.handle,
+                  "orbhip_search_loop_points")
+        except capi.OrbHipError as e:
+            e.partial, e.total = keys[:cap].copy(), npts.value
+            raise
+        m = npts.value
+        return keys[:m].copy(), (None if q is None else q[:m].copy()), na.value, nm.value, match[:n].copy()
+
     def search_last_frame_device(self, d_kps, d_desc, d_counts, cap, B, d_u_right, d_occupied, gp, d_cell_off, d_cell_idx, d_cam, d_slots,
                                  d_last_kps, d_motion, d_nq, cap_q, check_ori, th_high, d_queries, d_n_active, d_match, d_nmatches):
         """The batched, asynchronous form: every d_* is a device address (int; 0 where the header allows NULL); gp = (min_x,

@@ -941,6 +941,48 @@ int orbhip_search_loop_points(orbhip_ctx *ctx, const orbhip_fuse_target *target,
                               orbhip_proj_query *queries_out, int *n_active, int32_t *match, int *nmatches);
 int orbhip_map_kf_set_batch(orbhip_ctx *ctx, int m, const uint64_t *kf_keys, const int32_t *idx, const uint64_t *point_keys);
 
+/* ---- map points refreshed in place on the resident store ----
+ * MapPoint::ComputeDistinctiveDescriptors (ref: src/MapPoint.cc:257-322) and MapPoint::UpdateNormalAndDepth (ref: :345-386) for a
+ * batch of points, from their observation lists: the observers' descriptors and octaves are read from the resident feature sets, the
+ * position from the store, the camera centres from kfs.  The store's descriptor, normal and distance range are written in place and
+ * come back for the host objects as well.  One upload (8 B per point and 4 B of ref_pos, 8 B per observation, 32 B per key
+ * frame; no descriptors), one launch, one synchronisation.
+ *   prm        mvScaleFactors[nlevels], mnScaleLevels of the key frames; what = ORBHIP_REFRESH_DESC | ORBHIP_REFRESH_NORMAL
+ *   kfs [nkf]  the key frames the lists name: resident set, GetCameraCenter(), ORBHIP_KF_BAD = isBad()
+ *   point_keys [P]; off [P + 1] ascending from 0; obs_kf / obs_idx [off[P]]: observation j of point p is feature obs_idx[j] of key
+ *              frame kfs[obs_kf[j]], the list in ascending KeyFrame::mnId (docs/parity.md; the call never reorders it);
+ *              ref_pos [P]: the position of mpRefKF inside the point's list (read for ORBHIP_REFRESH_NORMAL only)
+ *   Descriptor half: observers with ORBHIP_KF_BAD are left out; if none remain the descriptor stays; otherwise the first row with the
+ *              least median sorted_row[(size_t)(0.5 * (N - 1))] wins.  best_pos [P] = its position in the list, or -1.
+ *   Normal and depth half: bad observers are NOT left out (the reference has no such test); arithmetic in docs/parity.md.
+ *   status [P] bit 0: descriptor set, bit 1: normal and depth set.  A point with ORBHIP_MP_BAD in the store, or with an empty list, is
+ *              left untouched: status 0.  desc_out [32 P], normal_out [3 P], min_dist_out, max_dist_out [P] hold the store's values
+ *              after the call, also for an untouched half.  Every output but status may be NULL.
+ *   ORBHIP_E_ARG, checked before any device work, nothing changed: an unknown point key or a key twice; a set that is not resident;
+ *   more distinct sets than the set limit in force; obs_kf / obs_idx out of range; ref_pos outside a non-empty list when
+ *   ORBHIP_REFRESH_NORMAL is asked; nlevels outside 1..16 or a set with an octave outside [0, nlevels); off not ascending from 0; what
+ *   outside 1..3.  ORBHIP_E_SIZE: a list of 2^20 rows or more.  P == 0: ORBHIP_OK.  Nothing is truncated.
+ * orbhip_map_get: read-back of n store entries; any output may be NULL; an unknown key is ORBHIP_E_ARG.  flags = ORBHIP_MP_*. */
+#define ORBHIP_REFRESH_DESC 1     /* ComputeDistinctiveDescriptors */
+#define ORBHIP_REFRESH_NORMAL 2   /* UpdateNormalAndDepth */
+#define ORBHIP_KF_BAD 1
+typedef struct {
+    uint64_t set_key;
+    float Ow[3];
+    uint32_t flags;
+} orbhip_refresh_kf;
+typedef struct {
+    float scale_factors[16];
+    int32_t nlevels;
+    int32_t what;
+} orbhip_refresh_params;
+int orbhip_map_refresh(orbhip_ctx *ctx, const orbhip_refresh_params *prm, int nkf, const orbhip_refresh_kf *kfs, int P,
+                       const uint64_t *point_keys, const int32_t *off, const int32_t *obs_kf, const int32_t *obs_idx,
+                       const int32_t *ref_pos, uint8_t *status, int32_t *best_pos, uint8_t *desc_out, float *normal_out,
+                       float *min_dist_out, float *max_dist_out);
+int orbhip_map_get(orbhip_ctx *ctx, int n, const uint64_t *keys, float *pos, float *normal, float *min_dist, float *max_dist,
+                   uint8_t *desc, uint8_t *flags);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

@@ -140,6 +140,24 @@ public:
     // for the tests: without the second search of changed survivors the result differs from the reference's
     static bool &ResearchChangedSurvivors() { static bool b = true; return b; }
 
+    // ---- map points refreshed in place on the resident store (orbhip_map_refresh) ----
+    // The loops "pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth();" over a key frame's points (ref:
+    // src/LocalMapping.cc:2036-2046, :2577-2590; the UpdateNormalAndDepth loops of src/Optimizer.cc with bDescriptors = false) as one
+    // device call: the lists are built from GetObservations() in ascending KeyFrame::mnId, the observers' features become resident
+    // sets (in ascending mnId, up to the set limit in force), and mDescriptor / mNormalVector / mfMinDistance / mfMaxDistance are
+    // assigned from what the call wrote into the store.  A point with an observer beyond the set limit, one that was never Put, or
+    // one whose mpRefKF is not among its observers goes the host way: the per-point methods, then one Put of all of them.  NULL
+    // entries, bad points, points without observations and second occurrences in vpMPs are skipped, as the reference's loop skips
+    // them.  The scale pyramid (mvScaleFactors, mnScaleLevels) is that of the first observer: one per SLAM session.  Returns the
+    // number of points touched: every point of vpMPs that was not skipped.
+    int RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDescriptors = true, bool bNormals = true);
+    // how many points the RefreshPoints calls of this process sent each way (for the tests and tools/refresh_latency.py)
+    struct RefreshWays { long device, host; };
+    static RefreshWays &RefreshCounts() { static RefreshWays w = {0, 0}; return w; }
+    // orbhip_set_limit for this object's context: how many key-frame sets stay resident (4 .. 96; 96 from the first Fuse or
+    // Refresh call on unless set here).  Returns the limit in force.
+    int SetLimit(int maxSets);
+
     // device of the objects constructed from now on (default 0)
     static void SetDevice(int device);
 
@@ -171,6 +189,7 @@ protected:
     size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
     size_t mnLastCandidates = 0, mnLastLoopPoints = 0;
     bool mbFuseSets = false;                   // the set limit has been raised for the targets of FuseInTargets
+    int mnSetLimit = 4;                        // the set limit in force (orbhip_set_limit)
 };
 
 }  // namespace ORB_SLAM2

@@ -70,6 +70,11 @@ public:
     // (src/MapPoint.cc:227); here it does so only while RecomputeOnReplace() is set, which the programs that test
     // LocalMapSearch::FuseInTargets do (a survivor's descriptor then changes between two targets, as in the reference).
     void ComputeDistinctiveDescriptors();
+    // ref: src/MapPoint.cc:345-386 (body below KeyFrame): mNormalVector, mfMinDistance, mfMaxDistance from the observers' camera
+    // centres and mpRefKF's feature, written with the explicit operations docs/parity.md fixes ("UpdateNormalAndDepth"); the
+    // observations are walked in ascending KeyFrame::mnId.  Nothing happens while mpRefKF is NULL.
+    void UpdateNormalAndDepth();
+    KeyFrame *mpRefKF = 0;                   // ref: include/MapPoint.h (protected there)
     static bool &RecomputeOnReplace() { static bool b = false; return b; }
 
     // ref: include/MapPoint.h "long unsigned int mnId; static long unsigned int nNextId;": mnId + 1 is the key under which
@@ -347,6 +352,46 @@ inline void MapPoint::ComputeDistinctiveDescriptors()
     for(int b=0; b<32; b++)
         d.ptr(0)[b] = rows[BestIdx].second[b];
     mDescriptor = d;
+}
+
+inline void MapPoint::UpdateNormalAndDepth()
+{
+    if(mbBad || mObservations.empty() || !mpRefKF)
+        return;
+    std::vector<std::pair<long unsigned int, KeyFrame *> > obs;
+    for(std::map<KeyFrame *, size_t>::iterator mit=mObservations.begin(), mend=mObservations.end(); mit!=mend; mit++)
+        obs.push_back(std::make_pair(mit->first->mnId, mit->first));
+    for(size_t i=1; i<obs.size(); i++)           // ascending mnId
+        for(size_t j=i; j>0 && obs[j].first<obs[j-1].first; j--)
+            std::swap(obs[j], obs[j-1]);
+    struct L2 {                                  // cv::norm(NORM_L2) of a CV_32F vector: summed in double, the root in double
+        static double norm(const float d[3]) { return std::sqrt(((double)d[0]*d[0] + (double)d[1]*d[1]) + (double)d[2]*d[2]); }
+    };
+    const float P[3] = {mWorldPos.at<float>(0, 0), mWorldPos.at<float>(1, 0), mWorldPos.at<float>(2, 0)};
+    float normal[3] = {0.f, 0.f, 0.f};
+    for(size_t i=0; i<obs.size(); i++)
+    {
+        const cv::Mat Owi = obs[i].second->GetCameraCenter();
+        const float d[3] = {P[0] - Owi.at<float>(0, 0), P[1] - Owi.at<float>(1, 0), P[2] - Owi.at<float>(2, 0)};
+        const float a = (float)(1.0 / L2::norm(d));                 // normali/norm: a MatExpr scaled by alpha = 1.0/norm
+        for(int c=0; c<3; c++)
+        {
+            const float t = d[c] * a;                               // normal + alpha*normali: scaleAdd on CV_32F
+            normal[c] = t + normal[c];
+        }
+    }
+    const cv::Mat Owr = mpRefKF->GetCameraCenter();
+    const float PC[3] = {P[0] - Owr.at<float>(0, 0), P[1] - Owr.at<float>(1, 0), P[2] - Owr.at<float>(2, 0)};
+    const float dist = (float)L2::norm(PC);
+    const size_t idx = mObservations.count(mpRefKF) ? mObservations[mpRefKF] : 0;   // (the reference's operator[] reads 0 as well)
+    const int level = mpRefKF->mvKeysUn[idx].octave;
+    const float inv = (float)(1.0 / (double)obs.size());           // normal/n: convertTo with a float scale
+    mfMaxDistance = dist * mpRefKF->mvScaleFactors[level];
+    mfMinDistance = mfMaxDistance / mpRefKF->mvScaleFactors[mpRefKF->mnScaleLevels-1];
+    cv::Mat nv(3, 1, CV_32F);
+    for(int c=0; c<3; c++)
+        nv.at<float>(c, 0) = normal[c] * inv;
+    mNormalVector = nv;
 }
 
 }  // namespace ORB_SLAM2

@@ -90,10 +90,11 @@ struct OrbSetView {
     const int32_t *d_cnt, *d_cellOff, *d_cellIdx;
 };
 bool orb_set_grid_view(orbhip_ctx *c, uint64_t key, OrbSetView *v);
-// the keypoint records of a resident set (with or without a grid) and the range of their octaves
+// the keypoint records and descriptors of a resident set (with or without a grid) and the range of their octaves
 struct OrbSetKps {
     int n, octMin, octMax;
     const orbhip_keypoint *d_kps;
+    const uint8_t *d_desc;
 };
 bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v);
 int orb_set_limit_in_force(orbhip_ctx *c);   // orbhip_set_limit: how many sets a call may name

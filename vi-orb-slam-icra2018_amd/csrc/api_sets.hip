@@ -104,7 +104,7 @@ bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v)
 {
     OrbSet *s = find_set(c, key);
     if (!s) return false;
-    *v = {s->n, s->octMin, s->octMax, s->d_kps};
+    *v = {s->n, s->octMin, s->octMax, s->d_kps, s->d_desc};
     return true;
 }
 

@@ -1,0 +1,164 @@
+// k_refresh.hip -- MapPoint::ComputeDistinctiveDescriptors (ref: src/MapPoint.cc:257-322) and MapPoint::UpdateNormalAndDepth
+// (ref: :345-386) for a batch of points of the resident store, in place.
+//   k_map_refresh   sixteen lanes per point, four points per wave, as k_distinctive (k_hamming.hip).  Observation j of a point
+//                   resolves through the call's key-frame table (descriptor base, keypoint base, camera centre, flags) to the
+//                   resident feature set: nothing is staged.  Descriptor half: lane i owns row i of the distance matrix of the
+//                   observers that are not bad (rows beyond 16 in further rounds), the row median by bisection on the value,
+//                   min over median << 20 | position.  Normal half: each lane forms its observers' scaled viewing directions, the
+//                   running sum is added in list order through a shuffle chain (docs/parity.md: order-dependent loops keep their
+//                   order).  Lane 0 writes geoA.w, geoB and the descriptor slot; flag word and generation are not touched.  The
+//                   kernel reads descriptors only from sets and positions only from geoA.xyz, and a slot occurs once per call, so
+//                   writing inside the launch is safe.
+//   k_map_gather    store entries by slot into one result block (orbhip_map_get).
+// Every float / double operation is individually rounded (docs/parity.md, "UpdateNormalAndDepth").
+#include "localmap_dev.h"
+
+// cv::norm(NORM_L2) of a CV_32F 3-vector: squares summed in double, the root in double
+__device__ __forceinline__ double norm3(float x, float y, float z)
+{
+    double sq = __dadd_rn(__dmul_rn((double)x, (double)x), __dmul_rn((double)y, (double)y));
+    sq = __dadd_rn(sq, __dmul_rn((double)z, (double)z));
+    return __dsqrt_rn(sq);
+}
+
+__global__ __launch_bounds__(256) void k_map_refresh(const RefreshKfDev *__restrict__ kfs, const orbhip_refresh_params *__restrict__ prm,
+                                                     const int32_t *__restrict__ slots, const int32_t *__restrict__ off,
+                                                     const int2 *__restrict__ obs, const int32_t *__restrict__ refPos, int P,
+                                                     int maxPoints, float4 *geoA, float4 *geoB, const uint32_t *__restrict__ mflags,
+                                                     uint4 *mdesc, uint8_t *__restrict__ status, int32_t *__restrict__ bestPos,
+                                                     uint4 *__restrict__ descOut, float4 *__restrict__ geoBOut,
+                                                     float *__restrict__ minOut)
+{
+    const int p = blockIdx.x * 16 + (threadIdx.x >> 4), lane = threadIdx.x & 15;
+    if (p >= P) return;
+    const int slot = slots[p];
+    if (slot < 0 || slot >= maxPoints) return;   // (the host resolves every key before the launch)
+    const int s = off[p], N = off[p + 1] - s;
+    const uint32_t fl = mflags[slot];
+    const float4 A = geoA[slot];
+    float4 B = geoB[slot];
+    float minDist = A.w;
+    uint4 D0 = mdesc[2 * (size_t)slot], D1 = mdesc[2 * (size_t)slot + 1];
+    const int what = prm->what;
+    const bool live = !(fl & ORBHIP_MP_BAD) && N > 0;
+    int st = 0, best = -1;
+
+    if (live && (what & ORBHIP_REFRESH_DESC)) {
+        int nb = 0;   // observers that are not bad
+        for (int j = lane; j < N; j += 16) nb += (kfs[obs[s + j].x].flags & ORBHIP_KF_BAD) ? 0 : 1;
+#pragma unroll
+        for (int d = 8; d >= 1; d >>= 1) nb += __shfl_xor(nb, d);
+        if (nb > 0) {
+            const int k = (int)(0.5 * (double)(nb - 1));
+            unsigned key = 0xffffffffu;
+            for (int i0 = 0; i0 < N; i0 += 16) {
+                const int i = i0 + lane;
+                if (i >= N) continue;
+                const int2 oi = obs[s + i];
+                if (kfs[oi.x].flags & ORBHIP_KF_BAD) continue;
+                const uint4 *Di = kfs[oi.x].desc + 2 * (size_t)oi.y;
+                const uint4 a0 = Di[0], a1 = Di[1];
+                int lo = 0, hi = 256;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    int cnt = 0;
+                    for (int j = 0; j < N; j++) {
+                        const int2 oj = obs[s + j];
+                        if (kfs[oj.x].flags & ORBHIP_KF_BAD) continue;
+                        const uint4 *Dj = kfs[oj.x].desc + 2 * (size_t)oj.y;
+                        cnt += hamming256(a0, a1, Dj[0], Dj[1]) <= mid;
+                    }
+                    if (cnt > k) hi = mid;
+                    else lo = mid + 1;
+                }
+                key = min(key, ((unsigned)lo << 20) | (unsigned)i);
+            }
+#pragma unroll
+            for (int d = 8; d >= 1; d >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, d));
+            best = (int)(key & 0xfffffu);
+            const int2 ob = obs[s + best];
+            const uint4 *Db = kfs[ob.x].desc + 2 * (size_t)ob.y;
+            D0 = Db[0], D1 = Db[1];
+            st |= ORBHIP_REFRESH_DESC;
+        }
+    }
+
+    if (live && (what & ORBHIP_REFRESH_NORMAL)) {
+        float nx = 0.f, ny = 0.f, nz = 0.f;
+        for (int i0 = 0; i0 < N; i0 += 16) {
+            const int i = i0 + lane;
+            float tx = 0.f, ty = 0.f, tz = 0.f;
+            if (i < N) {
+                const RefreshKfDev &K = kfs[obs[s + i].x];
+                const float dx = __fsub_rn(A.x, K.ox), dy = __fsub_rn(A.y, K.oy), dz = __fsub_rn(A.z, K.oz);
+                const float a = (float)__ddiv_rn(1.0, norm3(dx, dy, dz));   // normali / norm: a MatExpr scaled by 1.0 / norm
+                tx = __fmul_rn(dx, a), ty = __fmul_rn(dy, a), tz = __fmul_rn(dz, a);
+            }
+            const int m = min(16, N - i0);
+            for (int jj = 0; jj < m; jj++) {   // normal = normal + alpha * normali, in list order
+                nx = __fadd_rn(__shfl(tx, jj, 16), nx);
+                ny = __fadd_rn(__shfl(ty, jj, 16), ny);
+                nz = __fadd_rn(__shfl(tz, jj, 16), nz);
+            }
+        }
+        const float invN = (float)__ddiv_rn(1.0, (double)N);
+        const int2 orf = obs[s + min(max(refPos[p], 0), N - 1)];
+        const RefreshKfDev &R = kfs[orf.x];
+        const float dist = (float)norm3(__fsub_rn(A.x, R.ox), __fsub_rn(A.y, R.oy), __fsub_rn(A.z, R.oz));
+        const int level = min(max(R.kps[orf.y].octave, 0), ORBHIP_MAX_LEVELS - 1);
+        const int top = min(max(prm->nlevels - 1, 0), ORBHIP_MAX_LEVELS - 1);
+        B.x = __fmul_rn(nx, invN), B.y = __fmul_rn(ny, invN), B.z = __fmul_rn(nz, invN);
+        B.w = __fmul_rn(dist, prm->scale_factors[level]);
+        minDist = __fdiv_rn(B.w, prm->scale_factors[top]);
+        st |= ORBHIP_REFRESH_NORMAL;
+    }
+
+    if (lane == 0) {
+        if (st & ORBHIP_REFRESH_DESC) mdesc[2 * (size_t)slot] = D0, mdesc[2 * (size_t)slot + 1] = D1;
+        if (st & ORBHIP_REFRESH_NORMAL) {
+            reinterpret_cast<float *>(geoA)[4 * (size_t)slot + 3] = minDist;
+            geoB[slot] = B;
+        }
+        status[p] = (uint8_t)st;
+        bestPos[p] = best;
+        descOut[2 * (size_t)p] = D0, descOut[2 * (size_t)p + 1] = D1;
+        geoBOut[p] = B;
+        minOut[p] = minDist;
+    }
+}
+
+void launch_map_refresh(hipStream_t s, const RefreshKfDev *kfs, const orbhip_refresh_params *prm, const int32_t *slots,
+                        const int32_t *off, const void *obs, const int32_t *refPos, int P, int maxPoints, void *geoA, void *geoB,
+                        const uint32_t *mflags, void *mdesc, uint8_t *status, int32_t *bestPos, void *descOut, void *geoBOut,
+                        float *minOut)
+{
+    if (P <= 0) return;
+    hipLaunchKernelGGL(k_map_refresh, dim3((P + 15) / 16, 1, 1), dim3(256, 1, 1), 0, s, kfs, prm, slots, off, (const int2 *)obs, refPos, P,
+                       maxPoints, (float4 *)geoA, (float4 *)geoB, mflags, (uint4 *)mdesc, status, bestPos, (uint4 *)descOut,
+                       (float4 *)geoBOut, minOut);
+}
+
+__global__ __launch_bounds__(256) void k_map_gather(const int32_t *__restrict__ slots, int n, int maxPoints,
+                                                    const float4 *__restrict__ geoA, const float4 *__restrict__ geoB,
+                                                    const uint32_t *__restrict__ mflags, const uint4 *__restrict__ mdesc,
+                                                    float4 *__restrict__ aOut, float4 *__restrict__ bOut, uint4 *__restrict__ descOut,
+                                                    uint32_t *__restrict__ flagsOut)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int s = slots[i];
+    if (s < 0 || s >= maxPoints) return;
+    aOut[i] = geoA[s];
+    bOut[i] = geoB[s];
+    descOut[2 * (size_t)i] = mdesc[2 * (size_t)s];
+    descOut[2 * (size_t)i + 1] = mdesc[2 * (size_t)s + 1];
+    flagsOut[i] = mflags[s];
+}
+
+void launch_map_gather(hipStream_t s, const int32_t *slots, int n, int maxPoints, const void *geoA, const void *geoB,
+                       const uint32_t *mflags, const void *mdesc, void *aOut, void *bOut, void *descOut, uint32_t *flagsOut)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_map_gather, dim3((n + 255) / 256, 1, 1), dim3(256, 1, 1), 0, s, slots, n, maxPoints, (const float4 *)geoA,
+                       (const float4 *)geoB, mflags, (const uint4 *)mdesc, (float4 *)aOut, (float4 *)bOut, (uint4 *)descOut, flagsOut);
+}

@@ -526,6 +526,19 @@ void launch_map_flags(hipStream_t s, const int32_t *slot, const uint32_t *flags,
 void launch_local_frustum(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints,
                           const orbhip_local_camera *cams, const int32_t *slots, const uint8_t *skip, const int32_t *nq, int capQ,
                           int B, orbhip_local_point *points, orbhip_proj_query *queries, int32_t *nToMatch);
+// k_refresh.hip: one key frame of a refresh call as the kernel reads it, and the call's parameters
+struct RefreshKfDev {
+    const uint4 *desc;            // the resident set's descriptors
+    const orbhip_keypoint *kps;   // and keypoint records
+    float ox, oy, oz;             // GetCameraCenter()
+    uint32_t flags;               // ORBHIP_KF_BAD
+};
+void launch_map_refresh(hipStream_t s, const RefreshKfDev *kfs, const orbhip_refresh_params *prm, const int32_t *slots,
+                        const int32_t *off, const void *obs, const int32_t *refPos, int P, int maxPoints, void *geoA, void *geoB,
+                        const uint32_t *mflags, void *mdesc, uint8_t *status, int32_t *bestPos, void *descOut, void *geoBOut,
+                        float *minOut);
+void launch_map_gather(hipStream_t s, const int32_t *slots, int n, int maxPoints, const void *geoA, const void *geoB,
+                       const uint32_t *mflags, const void *mdesc, void *aOut, void *bOut, void *descOut, uint32_t *flagsOut);
 // k_projtrack.hip
 void launch_project_last_frame(hipStream_t s, const void *geoA, const uint32_t *mflags, int maxPoints, const orbhip_local_camera *cams,
                                const int32_t *slots, const orbhip_keypoint *lastKps, const int32_t *motion, const int32_t *nq, int capQ,

@@ -31,7 +31,7 @@ bool is_stereo(KeyFrame *pKF) { return !pKF->mvKeysUn.empty() && pKF->mvuRight.s
 bool LocalMapSearch::EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey)
 {
     if (!mbFuseSets) {
-        orbhip_set_limit(mpCtx, FUSE_SETS);
+        mnSetLimit = orbhip_set_limit(mpCtx, FUSE_SETS);
         mbFuseSets = true;
     }
     *setKey = set_key_of(pKF);

@@ -19,6 +19,9 @@ QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("proj_xr
                         ("max_level", "<i4"), ("angle", "<f4"), ("flags", "<i4")])   # orbhip_proj_query
 MOTION_SAME, MOTION_FORWARD, MOTION_BACKWARD = 0, 1, 2
 FUSE_TARGET_DTYPE = np.dtype([("set_key", "<u8"), ("cam", CAMERA_DTYPE), ("inv_level_sigma2", "<f4", 16)], align=True)   # orbhip_fuse_target
+REFRESH_DESC, REFRESH_NORMAL, KF_BAD = 1, 2, 1
+REFRESH_KF_DTYPE = np.dtype([("set_key", "<u8"), ("Ow", "<f4", 3), ("flags", "<u4")])   # orbhip_refresh_kf
+REFRESH_PARAMS_DTYPE = np.dtype([("scale_factors", "<f4", 16), ("nlevels", "<i4"), ("what", "<i4")])   # orbhip_refresh_params
 POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                         ("in_view", "<i4")])     # orbhip_local_point
 
@@ -299,6 +302,39 @@ class LocalMap:
             raise
         m = npts.value
         return keys[:m].copy(), (None if q is None else q[:m].copy()), na.value, nm.value, match[:n].copy()
+
+    # ---- map points refreshed in place: descriptor, normal, depth ----
+    def map_refresh(self, scale_factors, nlevels, what, kfs, point_keys, off, obs_kf, obs_idx, ref_pos, want=True):
+        """orbhip_map_refresh.  kfs: REFRESH_KF_DTYPE records; the lists as CSR (off [P + 1], obs_kf / obs_idx [off[P]]) in ascending
+        KeyFrame::mnId; ref_pos [P].  Returns (status, best_pos, desc, normal, min_dist, max_dist); with want=False every output but
+        status is passed as NULL and comes back None."""
+        prm = np.zeros(1, REFRESH_PARAMS_DTYPE)
+        sf = np.asarray(scale_factors, f32)
+        prm["scale_factors"][0][:len(sf)] = sf[:16]
+        prm["nlevels"], prm["what"] = nlevels, what
+        kfs = np.ascontiguousarray(kfs, REFRESH_KF_DTYPE)
+        pk = np.ascontiguousarray(point_keys, np.uint64).ravel()
+        off = np.ascontiguousarray(off, np.int32).ravel()
+        ok, oi = np.ascontiguousarray(obs_kf, np.int32).ravel(), np.ascontiguousarray(obs_idx, np.int32).ravel()
+        rp = np.ascontiguousarray(ref_pos, np.int32).ravel()
+        P = len(pk)
+        assert len(off) == P + 1 and len(rp) == P and len(ok) == len(oi)
+        m = max(P, 1)
+        status = np.zeros(m, np.uint8)
+        outs = [np.zeros(m, np.int32), np.zeros((m, 32), np.uint8), np.zeros((m, 3), f32), np.zeros(m, f32), np.zeros(m, f32)] if want else [None] * 5
+        check(self._L.orbhip_map_refresh(self._ctx.handle, _p(prm), len(kfs), _p(kfs), P, _p(pk), _p(off), _p(ok), _p(oi), _p(rp), _p(status),
+                                         *[_p(x) for x in outs]), self._ctx.handle, "orbhip_map_refresh")
+        return (status[:P].copy(),) + tuple(None if x is None else x[:P].copy() for x in outs)
+
+    def map_get(self, keys, want=("pos", "normal", "min_dist", "max_dist", "desc", "flags")):
+        """orbhip_map_get: the store's entries for keys, as a dict of the outputs named in want (the others are passed as NULL)."""
+        keys = np.ascontiguousarray(keys, np.uint64).ravel()
+        n, m = len(keys), max(len(keys), 1)
+        bufs = {"pos": np.zeros((m, 3), f32), "normal": np.zeros((m, 3), f32), "min_dist": np.zeros(m, f32), "max_dist": np.zeros(m, f32),
+                "desc": np.zeros((m, 32), np.uint8), "flags": np.zeros(m, np.uint8)}
+        args = [_p(bufs[k]) if k in want else None for k in ("pos", "normal", "min_dist", "max_dist", "desc", "flags")]
+        check(self._L.orbhip_map_get(self._ctx.handle, n, _p(keys), *args), self._ctx.handle, "orbhip_map_get")
+        return {k: bufs[k][:n].copy() for k in want}
 
     def search_last_frame_device(self, d_kps, d_desc, d_counts, cap, B, d_u_right, d_occupied, gp, d_cell_off, d_cell_idx, d_cam, d_slots,
                                  d_last_kps, d_motion, d_nq, cap_q, check_ori, th_high, d_queries, d_n_active, d_match, d_nmatches):

@@ -983,6 +983,23 @@ int orbhip_map_refresh(orbhip_ctx *ctx, const orbhip_refresh_params *prm, int nk
 int orbhip_map_get(orbhip_ctx *ctx, int n, const uint64_t *keys, float *pos, float *normal, float *min_dist, float *max_dist,
                    uint8_t *desc, uint8_t *flags);
 
+/* ---- the covisibility graph from the resident key-frame table ----
+ * KeyFrame::UpdateConnections (ref: src/KeyFrame.cc:731-812) for a batch of key frames.  w(q, j) = the number of points that are
+ * resolving entries (live, not ORBHIP_MP_BAD, of the entry's generation) of both row q and row j of the table above.
+ *   kf_keys [nq]   the key frames to update, nq <= 65536; a key twice gives the same answer twice; th >= 1 (the reference uses 15)
+ *   off_out [nq + 1]; entries off_out[q] .. off_out[q + 1] - 1 of nbr_keys_out / weights_out [cap] are the key frames j != q with
+ *                  w(q, j) > 0 in ascending key order: KFcounter, and so mConnectedKeyFrameWeights (docs/parity.md)
+ *   order_out [cap], nordered_out [nq]: order_out[off_out[q] + r], r < nordered_out[q], is the position within q's segment of the
+ *                  r-th element of mvpOrderedConnectedKeyFrames: the links of weight >= th, or, when there are none, the single
+ *                  link of greatest weight (the first maximum in ascending key order), in descending weight, ties by descending key
+ *   A query whose row is empty, or that shares nothing, has an empty segment and nordered_out[q] = 0.  *ntotal = off_out[nq].
+ * ORBHIP_E_ARG: a key the table does not know, th < 1, nq > 65536.  ORBHIP_E_CAPACITY: more than cap links; *ntotal has the number
+ * and nothing else is written.  ORBHIP_E_SIZE: nq times the number of key frames in the table above 2^30.  nq == 0: ORBHIP_OK,
+ * off_out[0] = 0.  A failed call changes nothing.  The queries go through the table 32 to a sweep, all sweeps in one call: one upload
+ * (4 B per query), one result block (8 B per link), one synchronisation.  Integer work: results are exact. */
+int orbhip_map_covis(orbhip_ctx *ctx, int nq, const uint64_t *kf_keys, int th, int32_t *off_out, uint64_t *nbr_keys_out,
+                     int32_t *weights_out, int32_t *order_out, int32_t *nordered_out, int cap, int *ntotal);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

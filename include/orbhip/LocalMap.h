@@ -154,6 +154,27 @@ public:
     // how many points the RefreshPoints calls of this process sent each way (for the tests and tools/refresh_latency.py)
     struct RefreshWays { long device, host; };
     static RefreshWays &RefreshCounts() { static RefreshWays w = {0, 0}; return w; }
+    // ---- the covisibility graph from the resident key-frame table (orbhip_map_covis; DESIGN.md section 20, INTEGRATION.md
+    // section 3e) ----
+    // KeyFrame::UpdateConnections (ref: src/KeyFrame.cc:731-843) for one key frame or for a batch: one device call counts the
+    // points every key frame of vpKFs shares with every key frame of the table, then the key frames are updated in the vector's
+    // order exactly as sequential pKF->UpdateConnections() calls would -- mConnectedKeyFrameWeights assigned, AddConnection on
+    // every neighbour of weight >= 15 (or on the single maximum), the two ordered lists assigned, the parent set on a key frame's
+    // first connection (mnId != 0).  The counts do not depend on that order: UpdateConnections edits neither points nor rows.
+    // Orders the reference takes from heap addresses are taken from mnId (docs/parity.md).  A key frame without a row is put.
+    // Precondition: every key frame that observes one of the points has its row in the table (PutKeyFrame for every new key
+    // frame); an erased key frame is nobody's neighbour.  A key frame that holds a non-NULL, non-bad point the store does not
+    // know goes the host way: pKF->UpdateConnections() itself.
+    // With pLoopConnections, what LoopClosing::CorrectLoop does per key frame (ref: src/LoopClosing.cc:600-616):
+    // (*pLoopConnections)[pKF] = the key frames of mConnectedKeyFrameWeights after the update, minus
+    // GetVectorCovisibleKeyFrames() from before it, minus *pvpExclude (mvpCurrentConnectedKFs).
+    void UpdateConnections(KeyFrame *pKF);
+    void UpdateConnections(const std::vector<KeyFrame *> &vpKFs, std::map<KeyFrame *, std::set<KeyFrame *> > *pLoopConnections = 0,
+                           const std::vector<KeyFrame *> *pvpExclude = 0);
+    // how many key frames the UpdateConnections calls of this process sent each way (for the tests and tools/covis_latency.py)
+    struct CovisWays { long device, host; };
+    static CovisWays &CovisCounts() { static CovisWays w = {0, 0}; return w; }
+
     // orbhip_set_limit for this object's context: how many key-frame sets stay resident (4 .. 96; 96 from the first Fuse or
     // Refresh call on unless set here).  Returns the limit in force.
     int SetLimit(int maxSets);
@@ -188,6 +209,7 @@ protected:
     bool mbKeyFrames = false;
     size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
     size_t mnLastCandidates = 0, mnLastLoopPoints = 0;
+    size_t mnLastLinks = 0;                    // links per key frame of the last UpdateConnections, rounded up
     bool mbFuseSets = false;                   // the set limit has been raised for the targets of FuseInTargets
     int mnSetLimit = 4;                        // the set limit in force (orbhip_set_limit)
 };

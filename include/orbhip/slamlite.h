@@ -6,6 +6,7 @@
 #ifndef ORBHIP_SLAMLITE_H
 #define ORBHIP_SLAMLITE_H
 
+#include <algorithm>
 #include <cmath>
 #include <map>
 #include <set>
@@ -263,6 +264,24 @@ public:
     KeyFrame *mpParent = 0;
     std::set<KeyFrame *> GetChilds() { return mspChildrens; }
     KeyFrame *GetParent() { return mpParent; }
+
+    // the covisibility graph as KeyFrame::UpdateConnections builds it (ref: src/KeyFrame.cc:528-562, :731-843; bodies below
+    // MapPoint's).  Where the reference orders by KeyFrame* (the walk of map<KeyFrame*, int>, the second member of the sorted
+    // pairs) the order here is that of mnId, so that equal weights resolve the same way in every process (docs/parity.md):
+    // mvpOrderedConnectedKeyFrames comes in descending weight, ties in descending mnId, and when no link reaches the threshold
+    // the first maximum in ascending mnId is taken.  A caller may still fill mvpOrderedConnectedKeyFrames by hand instead.
+    std::map<KeyFrame *, int> mConnectedKeyFrameWeights;
+    std::vector<int> mvOrderedWeights;
+    bool mbFirstConnection = true;
+    void AddChild(KeyFrame *pKF) { mspChildrens.insert(pKF); }
+    std::vector<KeyFrame *> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
+    std::vector<KeyFrame *> GetCovisiblesByWeight(const int &w);
+    int GetWeight(KeyFrame *pKF) { return mConnectedKeyFrameWeights.count(pKF) ? mConnectedKeyFrameWeights[pKF] : 0; }
+    void AddConnection(KeyFrame *pKF, const int &weight);
+    void UpdateBestCovisibles();       // lists EVERY entry of mConnectedKeyFrameWeights, the ones below the threshold included
+    void UpdateConnections();
+    // (weight, key frame) pairs -> the two ordered lists: sort() ascending by (weight, mnId), then read from the back
+    static void OrderCovisibles(std::vector<std::pair<int, KeyFrame *> > &vPairs, std::vector<KeyFrame *> &vpKFs, std::vector<int> &vWs);
 };
 
 inline int MapPoint::PredictScale(const float &currentDist, KeyFrame *pKF)
@@ -392,6 +411,110 @@ inline void MapPoint::UpdateNormalAndDepth()
     for(int c=0; c<3; c++)
         nv.at<float>(c, 0) = normal[c] * inv;
     mNormalVector = nv;
+}
+
+inline void KeyFrame::OrderCovisibles(std::vector<std::pair<int, KeyFrame *> > &vPairs, std::vector<KeyFrame *> &vpKFs, std::vector<int> &vWs)
+{
+    struct ByWeightThenId {                      // ascending (weight, mnId)
+        bool operator()(const std::pair<int, KeyFrame *> &a, const std::pair<int, KeyFrame *> &b) const
+        {
+            return a.first<b.first || (a.first==b.first && a.second->mnId<b.second->mnId);
+        }
+    };
+    std::sort(vPairs.begin(), vPairs.end(), ByWeightThenId());
+    vpKFs.clear();
+    vWs.clear();
+    for(size_t i=vPairs.size(); i>0; i--)        // push_front of each in turn
+    {
+        vpKFs.push_back(vPairs[i-1].second);
+        vWs.push_back(vPairs[i-1].first);
+    }
+}
+
+inline std::vector<KeyFrame *> KeyFrame::GetCovisiblesByWeight(const int &w)
+{
+    size_t n = 0;                                // mvOrderedWeights descends
+    while(n<mvOrderedWeights.size() && mvOrderedWeights[n]>=w)
+        n++;
+    return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin()+n);
+}
+
+inline void KeyFrame::AddConnection(KeyFrame *pKF, const int &weight)
+{
+    if(!mConnectedKeyFrameWeights.count(pKF))
+        mConnectedKeyFrameWeights[pKF]=weight;
+    else if(mConnectedKeyFrameWeights[pKF]!=weight)
+        mConnectedKeyFrameWeights[pKF]=weight;
+    else
+        return;
+    UpdateBestCovisibles();
+}
+
+inline void KeyFrame::UpdateBestCovisibles()
+{
+    std::vector<std::pair<int, KeyFrame *> > vPairs;
+    vPairs.reserve(mConnectedKeyFrameWeights.size());
+    for(std::map<KeyFrame *, int>::iterator mit=mConnectedKeyFrameWeights.begin(), mend=mConnectedKeyFrameWeights.end(); mit!=mend; mit++)
+        vPairs.push_back(std::make_pair(mit->second, mit->first));
+    OrderCovisibles(vPairs, mvpOrderedConnectedKeyFrames, mvOrderedWeights);
+}
+
+inline void KeyFrame::UpdateConnections()
+{
+    std::map<KeyFrame *, int> KFcounter;
+    const std::vector<MapPoint *> vpMP = mvpMapPoints;
+    for(size_t i=0; i<vpMP.size(); i++)
+    {
+        MapPoint *pMP = vpMP[i];
+        if(!pMP || pMP->isBad())
+            continue;
+        const std::map<KeyFrame *, size_t> observations = pMP->GetObservations();
+        for(std::map<KeyFrame *, size_t>::const_iterator mit=observations.begin(), mend=observations.end(); mit!=mend; mit++)
+        {
+            if(mit->first->mnId==mnId)
+                continue;
+            KFcounter[mit->first]++;
+        }
+    }
+    if(KFcounter.empty())
+        return;
+
+    const int th = 15;
+    std::vector<std::pair<long unsigned int, KeyFrame *> > byId;   // the counter walked in ascending mnId
+    for(std::map<KeyFrame *, int>::iterator mit=KFcounter.begin(), mend=KFcounter.end(); mit!=mend; mit++)
+        byId.push_back(std::make_pair(mit->first->mnId, mit->first));
+    std::sort(byId.begin(), byId.end());         // (mnId is unique)
+    int nmax = 0;
+    KeyFrame *pKFmax = NULL;
+    std::vector<std::pair<int, KeyFrame *> > vPairs;
+    for(size_t i=0; i<byId.size(); i++)
+    {
+        KeyFrame *pKFi = byId[i].second;
+        const int w = KFcounter[pKFi];
+        if(w>nmax)
+        {
+            nmax = w;
+            pKFmax = pKFi;
+        }
+        if(w>=th)
+        {
+            vPairs.push_back(std::make_pair(w, pKFi));
+            pKFi->AddConnection(this, w);
+        }
+    }
+    if(vPairs.empty())
+    {
+        vPairs.push_back(std::make_pair(nmax, pKFmax));
+        pKFmax->AddConnection(this, nmax);
+    }
+    mConnectedKeyFrameWeights = KFcounter;
+    OrderCovisibles(vPairs, mvpOrderedConnectedKeyFrames, mvOrderedWeights);
+    if(mbFirstConnection && mnId!=0)
+    {
+        mpParent = mvpOrderedConnectedKeyFrames.front();
+        mpParent->AddChild(this);
+        mbFirstConnection = false;
+    }
 }
 
 }  // namespace ORB_SLAM2

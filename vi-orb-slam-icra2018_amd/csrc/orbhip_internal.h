@@ -573,6 +573,9 @@ void launch_kf_set(hipStream_t s, const int64_t *at, const void *val, int m, int
 void launch_vote_rows(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint32_t *mflags, int maxPoints,
                       const uint32_t *marks, int capOut, int32_t *nout, int32_t *pairs);
 int collect_blocks(uint32_t P);
+// k_covis.hip: qrows [nq] = the table rows of the queries, 32 to a pass (mark, count, clear); *nout zero on entry
+void launch_covis(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint32_t *mflags, int maxPoints,
+                  uint32_t *marks, const int32_t *qrows, int nq, int capOut, int32_t *nout, void *trip);
 void launch_collect(hipStream_t s, const void *rows, int nrows, int stride, const int32_t *rowIdx, const uint32_t *off, int nkf,
                     uint32_t P, const uint32_t *mflags, int maxPoints, const uint32_t *marks, uint32_t *first, int32_t *cand,
                     int32_t *blockCnt, int capOut, int32_t *slots, uint8_t *skip, int32_t *nlocal);

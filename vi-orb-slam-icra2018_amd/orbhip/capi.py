@@ -72,7 +72,7 @@ SYMBOLS = [
     "orbhip_search_for_triangulation_sets",
     "orbhip_fuse_row", "orbhip_fuse_collect",
     "orbhip_fuse_sim3", "orbhip_search_loop_points", "orbhip_map_kf_set_batch",
-    "orbhip_map_refresh", "orbhip_map_get",
+    "orbhip_map_refresh", "orbhip_map_get", "orbhip_map_covis",
 ]
 
 
@@ -255,6 +255,7 @@ def load():
     L.orbhip_map_kf_set_batch.argtypes = [vp, i32, vp, vp, vp]
     L.orbhip_map_refresh.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_get.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbhip_map_covis.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, ip]
     L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
     L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]

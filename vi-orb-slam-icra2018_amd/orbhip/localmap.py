@@ -171,6 +171,30 @@ class LocalMap:
             raise
         return out[:n.value].copy()
 
+    def covis(self, kf_keys, th=15, cap=None):
+        """orbhip_map_covis (DESIGN.md section 20): KeyFrame::UpdateConnections' counts and lists for every key frame of kf_keys.
+        Returns one (keys, weights, ordered_keys) triple per query: the key frames that share a point with it in ascending key
+        order with their weights (mConnectedKeyFrameWeights), and mvpOrderedConnectedKeyFrames as keys.  cap: room for the links of
+        all queries together (default: queries times live key frames, which always suffices)."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        nq = len(kk)
+        cap = nq * self.kf_info()[0] if cap is None else cap
+        off, nord = np.full(nq + 1, -1, np.int32), np.full(max(nq, 1), -1, np.int32)
+        nbr, w, order = np.zeros(max(cap, 1), np.uint64), np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), -1, np.int32)
+        n = C.c_int(-1)
+        try:
+            check(self._L.orbhip_map_covis(self._ctx.handle, nq, _p(kk), th, _p(off), _p(nbr), _p(w), _p(order), _p(nord), cap,
+                                           C.byref(n)), self._ctx.handle, "orbhip_map_covis")
+        except capi.OrbHipError as e:     # too little room: .total has the number, .outputs what the call left in its outputs
+            e.total, e.outputs = n.value, (off, nbr, w, order, nord)
+            raise
+        assert n.value == off[nq]
+        out = []
+        for q in range(nq):
+            a, b = int(off[q]), int(off[q + 1])
+            out.append((nbr[a:b].copy(), w[a:b].copy(), nbr[a:b][order[a:a + nord[q]]].copy()))
+        return out
+
     def track(self, frame_key, n, cam, kf_keys, seen_keys, cap, nnratio=0.8, u_right=None, occupied=None):
         """collect + search in one call.  Returns (local_keys, points, n_to_match, nmatches, match)."""
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)

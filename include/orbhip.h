@@ -1000,6 +1000,42 @@ int orbhip_map_get(orbhip_ctx *ctx, int n, const uint64_t *keys, float *pos, flo
 int orbhip_map_covis(orbhip_ctx *ctx, int nq, const uint64_t *kf_keys, int th, int32_t *off_out, uint64_t *nbr_keys_out,
                      int32_t *weights_out, int32_t *order_out, int32_t *nordered_out, int cap, int *ntotal);
 
+/* ---- SearchByBoW against all candidate key frames in one call ----
+ * Tracking::Relocalization (ref: src/Tracking.cc:2595-2616) and LoopClosing::ComputeSim3 (ref: src/LoopClosing.cc:304-332) call
+ * ORBmatcher::SearchByBoW once per candidate key frame.  Here one call matches the fixed side against K candidates: every key frame
+ * is a resident set (orbhip_set_put), and "feature i has a map point that is not bad" is what the key frame's row of the table
+ * above answers -- entry i resolves (live, not ORBHIP_MP_BAD, of the entry's generation) -- so no validity bytes travel.
+ *   mode 0   SearchByBoW(pKF_k, F) (ref: src/ORBmatcher.cc:159-288): the fixed set is the frame and takes side 2, every feature of it
+ *            counts, fixed_row_key is ignored; candidate k takes side 1; a match needs dist <= th.  matches[k][iF] = the key frame's
+ *            feature matched to frame feature iF, or -1: vpMapPointMatches of call k as indices.
+ *   mode 1   SearchByBoW(pCurrentKF, pKF_k) (:522-655): the fixed set is the current key frame and takes side 1, valid through
+ *            fixed_row_key; candidate k takes side 2; dist < th.  matches[k][i1] = the candidate's feature, or -1: vpMatches12.
+ *   matches [K][n_fixed], nmatches [K] (after the rotation check when check_ori != 0).  Row k and nmatches[k] equal what
+ *   orbhip_search_by_bow_sets returns for that pair (match21 in mode 0, match12 in mode 1) with validity bytes derived from the same
+ *   rows at the same moment and th_mode = mode.  A candidate may appear twice (two equal rows); a candidate may be the fixed set.
+ * Mode 0 only, all of level_sigma2 .. max_err and ntotal NULL to skip: what PnPsolver::PnPsolver (ref: src/PnPsolver.cc:78-101) and
+ * the mvMaxError loop of SetRansacParameters (:154-156) build, for every candidate with nmatches[k] >= min_matches, in the layout
+ * orbhip_pnp_score takes.  Candidate k owns entries off[k] .. off[k + 1] - 1 (off [K + 1]; an empty segment below min_matches), the
+ * frame's features in ascending index: kp_idx = the frame feature i (mvKeyPointIndices), kf_idx = the matched key-frame feature j,
+ * P2D [.][2] = the frame set's keypoint position, max_err = level_sigma2[octave_i] * th2 (a float product), P3Dw [.][3] = the store's
+ * position of the point row entry j resolves to.  *ntotal = off[K]; cap = the capacity of the five arrays in entries,
+ * K * n_fixed always suffices.
+ * Limits: K <= 4095 (the pair record keeps the candidate in 12 bits, its FeatureVector node in 20); K * n_fixed < 2^31.
+ * Errors, checked before any device work -- a failed call writes nothing and leaves the context usable.  ORBHIP_E_ARG: an unknown
+ * set or row key, a row whose length differs from its set's n, more distinct sets than orbhip_set_limit allows, K < 0 or > 4095, a
+ * mode other than 0 / 1, gather outputs in mode 1 or only some of them, nlevels outside 1..64, a frame octave outside [0, nlevels).
+ * ORBHIP_E_SIZE: a side-2 FeatureVector of 2^20 entries or more.  ORBHIP_E_CAPACITY: cap < *ntotal; *ntotal is set and nothing else
+ * is written.  K == 0: ORBHIP_OK, nothing is written.  Integer work but for the histogram's float bin and max_err: exact. */
+typedef struct orbhip_bow_candidate {
+    uint64_t set_key, row_key;
+} orbhip_bow_candidate;
+int orbhip_search_by_bow_candidates(orbhip_ctx *ctx, int mode, uint64_t fixed_set_key, uint64_t fixed_row_key,
+                                    const orbhip_bow_candidate *cand, int K, int th, float nnratio, int check_ori,
+                                    int32_t *matches /* [K][n_fixed] */, int32_t *nmatches /* [K] */,
+                                    /* mode 0 only, all NULL to skip: */ int min_matches, const float *level_sigma2, int nlevels,
+                                    float th2, int32_t *off /* [K+1] */, int32_t *kp_idx, int32_t *kf_idx, float *P3Dw, float *P2D,
+                                    float *max_err, int cap, int *ntotal);
+
 /* ---- colour frames in, depth at the keypoints out: the RGB-D sensor path (new) ----
  * Every Tracking::GrabImage* converts a 3- or 4-channel image to grey with cvtColor before the extractor sees it (ref:
  * src/Tracking.cc:869-894, 909-922, 939-952), and GrabImageRGBD converts the whole depth map with

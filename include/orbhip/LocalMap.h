@@ -25,8 +25,34 @@
 
 struct orbhip_ctx;
 
+#ifndef ORBHIP_WITH_REFERENCE_HEADERS
+#ifndef ORBHIP_CVLITE_POINT3F
+#define ORBHIP_CVLITE_POINT3F
+namespace cv
+{
+template <typename T> struct Point3_ {
+    T x, y, z;
+    Point3_() : x(0), y(0), z(0) {}
+    Point3_(T _x, T _y, T _z) : x(_x), y(_y), z(_z) {}
+};
+typedef Point3_<float> Point3f;
+}  // namespace cv
+#endif
+#endif
+
 namespace ORB_SLAM2
 {
+
+// What PnPsolver::PnPsolver(F, vpMapPointMatches) and the mvMaxError loop of SetRansacParameters build for one candidate key frame
+// (ref: src/PnPsolver.cc:78-101, :154-156), in the form RansacScore::ScorePnP takes: one entry per frame feature that holds a
+// matched point, in ascending feature index.  Empty for a candidate below minMatches.
+struct RelocCorrespondences
+{
+    std::vector<cv::Point2f> mvP2D;
+    std::vector<float> mvMaxError;               // mvSigma2[i] * th2
+    std::vector<cv::Point3f> mvP3Dw;
+    std::vector<size_t> mvKeyPointIndices;
+};
 
 class LocalMapSearch
 {
@@ -175,6 +201,28 @@ public:
     struct CovisWays { long device, host; };
     static CovisWays &CovisCounts() { static CovisWays w = {0, 0}; return w; }
 
+    // ---- SearchByBoW against all candidate key frames in one call (orbhip_search_by_bow_candidates; DESIGN.md section 21,
+    // INTEGRATION.md section 3e) ----
+    // The loop of Tracking::Relocalization (ref: src/Tracking.cc:2595-2616): matcher.SearchByBoW(pKF, F, vvpMapPointMatches[i]) for
+    // every candidate, matcher = ORBmatcher(nnratio, checkOri).  vvpMapPointMatches[i] and vnMatches[i] are what the call leaves and
+    // returns; a candidate with isBad() gets an empty vector and 0.  With pvSetups, (*pvSetups)[i] holds what the PnPsolver
+    // constructor and SetRansacParameters(.., th2) would gather for every candidate with vnMatches[i] >= minMatches.  All candidates
+    // are matched in one device call (as many as the set limit allows beyond that): the key frames' features are resident sets
+    // (put here the first time), "has a point that is not bad" is read from their rows of the table, the positions from the store.
+    // Indices are turned back into MapPoint* from GetMapPointMatches() at the moment of application.  A candidate that holds a
+    // non-NULL, non-bad point the store does not know goes the host way, through ORBmatcher::SearchByBoW and the host loop.
+    void SearchByBoWCandidates(const std::vector<KeyFrame *> &vpCandidateKFs, Frame &F, std::vector<std::vector<MapPoint *> > &vvpMapPointMatches,
+                               std::vector<int> &vnMatches, std::vector<RelocCorrespondences> *pvSetups = 0, int minMatches = 15,
+                               float th2 = 5.991, float nnratio = 0.75, bool checkOri = true);
+    // The loop of LoopClosing::ComputeSim3 (ref: src/LoopClosing.cc:304-332): matcher.SearchByBoW(pCurrentKF, pKF, vvpMatches12[i]) for
+    // every candidate.  When pCurrentKF holds a point the store does not know, every candidate goes the host way.
+    void SearchByBoWCandidates(KeyFrame *pCurrentKF, const std::vector<KeyFrame *> &vpCandidateKFs,
+                               std::vector<std::vector<MapPoint *> > &vvpMatches12, std::vector<int> &vnMatches, float nnratio = 0.75,
+                               bool checkOri = true);
+    // how many candidates the SearchByBoWCandidates calls of this process sent each way (for the tests and tools/bowcand_latency.py)
+    struct BowCandWays { long device, host; };
+    static BowCandWays &BowCandCounts() { static BowCandWays w = {0, 0}; return w; }
+
     // orbhip_set_limit for this object's context: how many key-frame sets stay resident (4 .. 96; 96 from the first Fuse or
     // Refresh call on unless set here).  Returns the limit in force.
     int SetLimit(int maxSets);
@@ -201,6 +249,7 @@ protected:
     void FuseRowEdits(const FuseEdits &edits, FuseRows &rows);    // the table's half, as lists per key frame
     bool FlushLoop(FuseEdits &edits);                             // FlushFuse with one orbhip_map_kf_set_batch (LocalMapLoop.cc)
     bool EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey);
+    bool ResidentKeyFrame(KeyFrame *pKF, uint64_t *setKey);       // SearchByBoWCandidates: row and set of a key frame the store knows (LocalMapBowCand.cc)
 
     orbhip_ctx *mpCtx;
     std::mutex mMutex;

@@ -139,7 +139,7 @@ public:
     std::vector<bool> mvbOutlier;
     std::vector<std::size_t> mGrid[FRAME_GRID_COLS][FRAME_GRID_ROWS];
     cv::Mat mTcw;                            // 4 x 4 CV_32F
-    std::vector<float> mvScaleFactors;
+    std::vector<float> mvScaleFactors, mvLevelSigma2;   // (mvLevelSigma2: read by PnPsolver::PnPsolver, ref: src/PnPsolver.cc:90)
     int mnScaleLevels;                       // ref: src/Frame.cc:61-63 (mfLogScaleFactor = log(mfScaleFactor), float)
     float mfScaleFactor, mfLogScaleFactor;
     cv::Mat mK;                              // 3 x 3 CV_32F

@@ -97,6 +97,16 @@ struct OrbSetKps {
     const uint8_t *d_desc;
 };
 bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v);
+// what a SearchByBoW over resident sets needs of one: the FeatureVector as CSR on the device and its host mirror (valid until the
+// set is replaced or evicted, which no search does)
+struct OrbSetBow {
+    int n, ng, octMin, octMax;
+    const orbhip_keypoint *d_kps;
+    const uint8_t *d_desc;
+    const int32_t *d_off, *d_idx;
+    const int32_t *node, *off;   // host: node[ng], off[ng + 1]
+};
+bool orb_set_bow_view(orbhip_ctx *c, uint64_t key, OrbSetBow *v);
 int orb_set_limit_in_force(orbhip_ctx *c);   // orbhip_set_limit: how many sets a call may name
 static inline bool grid_params_ok(float inv_w, float inv_h) { return inv_w > 0.f && inv_h > 0.f; }
 

@@ -108,6 +108,14 @@ bool orb_set_kps_view(orbhip_ctx *c, uint64_t key, OrbSetKps *v)
     return true;
 }
 
+bool orb_set_bow_view(orbhip_ctx *c, uint64_t key, OrbSetBow *v)
+{
+    OrbSet *s = find_set(c, key);
+    if (!s) return false;
+    *v = {s->n, s->ng, s->octMin, s->octMax, s->d_kps, s->d_desc, s->d_off, s->d_idx, s->node.data(), s->off.data()};
+    return true;
+}
+
 int orb_set_limit_in_force(orbhip_ctx *c) { return table(c)->limit; }
 
 extern "C" int orbhip_set_has(orbhip_ctx *c, uint64_t key, int n)

@@ -19,12 +19,12 @@
 // Integer/bitwise path (XOR + popcount); no MFMA.
 #include "orbhip_internal.h"
 #include "wave_ops.h"
+#include "bow_rot_dev.h"   // BS_HISTO, bow_rot_bin, bow_three_maxima, bow_rot_keeps
 
 #include <type_traits>
 
 #include <cstdlib>
 
-#define BS_HISTO 30
 
 #define BS_THREADS 1024   // threads per workgroup of k_bow_seq (its launch bound)
 
@@ -438,38 +438,13 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
         for (int i1 = tid; i1 < n1; i1 += blockDim.x) {
             const int i2 = m12[i1];
             if (i2 >= 0) {
-                float rot = k1[i1].angle - k2[i2].angle;
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * (1.0f / BS_HISTO));
-                if (bin == BS_HISTO) bin = 0;
+                const int bin = bow_rot_bin(k1[i1].angle, k2[i2].angle);
                 if (bin >= 0 && bin < BS_HISTO) atomicAdd(&s_hist[bin], 1);
             }
         }
         __syncthreads();
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < BS_HISTO; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    i3 = i;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                i2 = -1;
-                i3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                i3 = -1;
-            }
-            s_keep[0] = i1;
-            s_keep[1] = i2;
-            s_keep[2] = i3;
+            bow_three_maxima(s_hist, s_keep);
         }
         __syncthreads();
     }
@@ -481,11 +456,7 @@ __global__ __launch_bounds__(BS_THREADS) void k_bow_seq(const uint8_t *__restric
     for (int i1 = tid; i1 < cap; i1 += blockDim.x) {
         int i2 = i1 < n1 ? m12[i1] : -1;
         if (i2 >= 0 && check_ori) {
-            float rot = k1[i1].angle - k2[i2].angle;
-            if (rot < 0.0f) rot += 360.0f;
-            int bin = (int)roundf(rot * (1.0f / BS_HISTO));
-            if (bin == BS_HISTO) bin = 0;
-            if (bin >= 0 && bin < BS_HISTO && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) i2 = -1;
+            if (!bow_rot_keeps(bow_rot_bin(k1[i1].angle, k2[i2].angle), s_keep)) i2 = -1;
         }
         o12[i1] = i2;
         if (i2 >= 0) {
@@ -1000,13 +971,7 @@ rotation:
 
     // ---- 7. rotation consistency (:267-285) and outputs ----
     const orbhip_keypoint *k1p = kps + (size_t)b1 * cap, *k2p = kps + (size_t)b * cap;
-    auto bin_of = [&](int i1, int i2) {
-        float rot = k1p[i1].angle - k2p[i2].angle;
-        if (rot < 0.0f) rot += 360.0f;
-        int bin = (int)roundf(rot * (1.0f / BS_HISTO));
-        if (bin == BS_HISTO) bin = 0;
-        return bin;
-    };
+    auto bin_of = [&](int i1, int i2) { return bow_rot_bin(k1p[i1].angle, k2p[i2].angle); };
     if (check_ori) {
         for (int i1 = tid; i1 < n1; i1 += BL_THREADS) {
             const int i2 = m12[i1];
@@ -1017,29 +982,7 @@ rotation:
         }
         __syncthreads();
         if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < BS_HISTO; i++) {
-                const int sz = s_hist[i];
-                if (sz > max1) {
-                    max3 = max2; max2 = max1; max1 = sz;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (sz > max2) {
-                    max3 = max2; max2 = sz;
-                    i3 = i2; i2 = i;
-                } else if (sz > max3) {
-                    max3 = sz;
-                    i3 = i;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                i2 = -1;
-                i3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                i3 = -1;
-            }
-            s_keep[0] = i1;
-            s_keep[1] = i2;
-            s_keep[2] = i3;
+            bow_three_maxima(s_hist, s_keep);
         }
         __syncthreads();
     }
@@ -1051,7 +994,7 @@ rotation:
         if (i2 == 0xFFFF) i2 = -1;
         if (i2 >= 0 && check_ori) {
             const int bin = bin_of(i1, i2);
-            if (bin >= 0 && bin < BS_HISTO && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) i2 = -1;
+            if (!bow_rot_keeps(bin, s_keep)) i2 = -1;
         }
         o12[i1] = i2;
         if (i2 >= 0) {

@@ -608,6 +608,30 @@ void launch_tri_match_sets(hipStream_t s, const orbhip_keypoint *kps1, const uin
                            const int32_t *off1, const int32_t *idx1, int n1, const TriNeighbourDev *nbs, const uint8_t *skip2cat,
                            const float *ur2cat, const TriPair *pairs, int npairs, bool anyRegister, bool anyStrided,
                            const float *scale2, const float *sigma2, int32_t *match12);
+// k_bowcand.hip: SearchByBoW of one fixed side against K candidates -- one record per candidate in device memory, one per shared node
+struct BowCandDev {
+    const uint8_t *desc;
+    const int32_t *off, *idx;
+    const orbhip_keypoint *kps;
+    const void *row;         // int2: its row of the key-frame table ([0].x = length, [1 + i] = {slot, generation})
+    int n;                   // features of its set
+    int scratchOff;          // first element of its candidate-indexed (reverse) array in the scratch
+    int outRow, pad;         // its row of the [K][nFixed] arrays
+};
+#define BOW_CAND_NODE_BITS 20    // a candidate's FeatureVector has fewer than 2^20 nodes ...
+#define BOW_CAND_MAX_K 4095      // ... and the candidate index takes the other 12 bits of the pair record
+struct BowCandPair {
+    uint32_t gFixed, gk;     // node of the fixed side; candidate k << BOW_CAND_NODE_BITS | node of candidate k
+};
+void launch_bow_match_cands(hipStream_t s, int mode, const uint8_t *descF, const int32_t *offF, const int32_t *idxF, const void *rowF,
+                            int nF, const BowCandDev *cands, const BowCandPair *pairs, int npairs, const uint32_t *mflags,
+                            int maxPoints, int th, float nnratio, int32_t *out, int32_t *scratch);
+void launch_bow_rot_cands(hipStream_t s, int mode, const BowCandDev *cands, int K, const orbhip_keypoint *kpsF, int nF, int check_ori,
+                          int32_t *out, int32_t *hostRows, int32_t *nm, int32_t *hostNm);
+void launch_pnp_gather_cands(hipStream_t s, const BowCandDev *cands, int K, const int32_t *nm, int minMatches,
+                             const orbhip_keypoint *kpsF, int nF, const int32_t *out, const float *levelSigma2, int nlevels, float th2,
+                             const void *geoA, const uint32_t *mflags, int maxPoints, int cap, int32_t *off, int32_t *ntotal,
+                             int32_t *kpIdx, int32_t *kfIdx, float *P3Dw, float *P2D, float *maxErr);
 size_t init_scratch_bytes(int B, int cap1, int cap2);
 size_t init_assign_lds(int cap1, int cap2);
 int launch_search_for_initialization(hipStream_t s, const orbhip_keypoint *kps1, const uint8_t *desc1, const int32_t *cnt1,

@@ -72,7 +72,7 @@ SYMBOLS = [
     "orbhip_search_for_triangulation_sets",
     "orbhip_fuse_row", "orbhip_fuse_collect",
     "orbhip_fuse_sim3", "orbhip_search_loop_points", "orbhip_map_kf_set_batch",
-    "orbhip_map_refresh", "orbhip_map_get", "orbhip_map_covis",
+    "orbhip_map_refresh", "orbhip_map_get", "orbhip_map_covis", "orbhip_search_by_bow_candidates",
 ]
 
 
@@ -81,6 +81,7 @@ class FrameParams(C.Structure):   # orbhip_frame_params
                 ("inv_w", C.c_float), ("inv_h", C.c_float), ("levelsup", C.c_int)]
 
 
+BOW_CANDIDATE_DTYPE = np.dtype([("set_key", "<u8"), ("row_key", "<u8")])   # orbhip_bow_candidate
 TRI_NEIGHBOUR_DTYPE = np.dtype([("key2", "<u8"), ("F12", "<f4", (9,)), ("ex", "<f4"), ("ey", "<f4")], align=True)   # orbhip_tri_neighbour
 QUERY_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("radius", "<f4"), ("proj_xr", "<f4"), ("min_level", "<i4"),
                         ("max_level", "<i4"), ("angle", "<f4"), ("flags", "<i4")])   # orbhip_proj_query
@@ -256,6 +257,8 @@ def load():
     L.orbhip_map_refresh.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_get.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_covis.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, ip]
+    L.orbhip_search_by_bow_candidates.argtypes = [vp, i32, u64, u64, vp, i32, i32, f32, i32, vp, vp, i32, vp, i32, f32, vp, vp, vp,
+                                                  vp, vp, vp, i32, ip]
     L.orbhip_grey.argtypes = [vp, vp, i32, i32, i32, i32, vp, i32]
     L.orbhip_grey_device.argtypes = [vp, vp, i32, i32, i32, i32, C.c_size_t, i32, vp, i32, C.c_size_t]
     L.orbhip_extract_color.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, ip, vp]

@@ -195,6 +195,46 @@ class LocalMap:
             out.append((nbr[a:b].copy(), w[a:b].copy(), nbr[a:b][order[a:a + nord[q]]].copy()))
         return out
 
+    def search_by_bow_candidates(self, mode, fixed_set_key, fixed_row_key, n_fixed, candidates, th=50, nnratio=0.75, check_ori=True,
+                                 gather=None, cap=None):
+        """orbhip_search_by_bow_candidates: SearchByBoW of the fixed set of n_fixed features against K
+        candidates, candidates = [(set_key, row_key), ...].  mode 0: SearchByBoW(pKF_k, F), mode 1: SearchByBoW(pCurrentKF, pKF_k).
+        gather (mode 0): None, or (min_matches, level_sigma2, th2) for the PnPsolver arrays; cap: their room in entries (default
+        K * n_fixed).  Returns (matches [K][n_fixed], nmatches [K]) and, with gather, a dict off / kp_idx / kf_idx / P3Dw / P2D /
+        max_err behind them.  The buffers start as -7 so that a caller sees what a failed call left alone (e.outputs)."""
+        cd = np.zeros(max(len(candidates), 1), capi.BOW_CANDIDATE_DTYPE)
+        K = len(candidates)
+        for k, (sk, rk) in enumerate(candidates):
+            cd["set_key"][k], cd["row_key"][k] = sk, rk
+        matches, nm = np.full(max(K * n_fixed, 1), -7, np.int32), np.full(max(K, 1), -7, np.int32)
+        if gather is None:
+            args = [0, None, 0, f32(0), None, None, None, None, None, None, 0, None]
+            outs = (matches, nm)
+        else:
+            min_matches, sigma2, th2 = gather
+            sigma2 = np.ascontiguousarray(sigma2, f32)
+            cap = K * n_fixed if cap is None else cap
+            m = max(cap, 1)
+            off, kp, kf = np.full(K + 1, -7, np.int32), np.full(m, -7, np.int32), np.full(m, -7, np.int32)
+            P3, P2, me = np.full((m, 3), -7, f32), np.full((m, 2), -7, f32), np.full(m, -7, f32)
+            nt = C.c_int(-7)
+            args = [min_matches, _p(sigma2), len(sigma2), f32(th2), _p(off), _p(kp), _p(kf), _p(P3), _p(P2), _p(me), cap, C.byref(nt)]
+            outs = (matches, nm, off, kp, kf, P3, P2, me)
+        try:
+            check(self._L.orbhip_search_by_bow_candidates(self._ctx.handle, mode, fixed_set_key, fixed_row_key, _p(cd), K, th, f32(nnratio),
+                                                          1 if check_ori else 0, _p(matches), _p(nm), *args), self._ctx.handle,
+                  "orbhip_search_by_bow_candidates")
+        except capi.OrbHipError as e:
+            e.total, e.outputs = (None if gather is None else nt.value), outs
+            raise
+        res = (matches[:K * n_fixed].reshape(K, n_fixed).copy(), nm[:K].copy())
+        if gather is None or K == 0:
+            return res
+        t = nt.value
+        assert t == off[K]
+        return res + ({"off": off.copy(), "kp_idx": kp[:t].copy(), "kf_idx": kf[:t].copy(), "P3Dw": P3[:t].copy(), "P2D": P2[:t].copy(),
+                       "max_err": me[:t].copy()},)
+
     def track(self, frame_key, n, cam, kf_keys, seen_keys, cap, nnratio=0.8, u_right=None, occupied=None):
         """collect + search in one call.  Returns (local_keys, points, n_to_match, nmatches, match)."""
         cam = np.ascontiguousarray(cam, CAMERA_DTYPE)

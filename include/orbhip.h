@@ -1000,6 +1000,43 @@ int orbhip_map_get(orbhip_ctx *ctx, int n, const uint64_t *keys, float *pos, flo
 int orbhip_map_covis(orbhip_ctx *ctx, int nq, const uint64_t *kf_keys, int th, int32_t *off_out, uint64_t *nbr_keys_out,
                      int32_t *weights_out, int32_t *order_out, int32_t *nordered_out, int cap, int *ntotal);
 
+/* ---- the counts of KeyFrameCulling from the resident key-frame table ----
+ * LocalMapping::KeyFrameCulling and KeyFrameCullingForMonoVI (ref: src/LocalMapping.cc:2692-2756, :1477-1584) count, for every
+ * covisible key frame, the map points it sees and those of them that at least th_obs other key frames see at the same or a finer
+ * scale.  Three facts about feature i of a key frame that the rows do not hold travel once, as one level byte per row entry:
+ *   bits 0..3  mvKeysUn[i].octave (0..15)       bit 6  mvuRight[i] >= 0: the observation counts twice in MapPoint::nObs
+ *   bit 7      mvDepth[i] > mThDepth || mvDepth[i] < 0: a far stereo point      bits 4, 5  must be 0
+ * orbhip_map_kf_levels: the levels of m key frames in one upload, bytes [off[m]], row q = bytes[off[q] .. off[q + 1]) covers features
+ * 0 .. off[q + 1] - off[q] - 1.  The device array ([max_kfs][max_row] bytes) is allocated by the first call.  A row keeps its levels
+ * through orbhip_map_kf_put / _set of the same key (a key frame's features do not change) and loses them when it is erased, when
+ * its row goes to another key, and in orbhip_map_kf_clear / orbhip_map_kf_init / orbhip_map_init.  A row longer than its levels
+ * counts as without.  ORBHIP_E_ARG, nothing changed: an unknown key, a key twice in the call, a segment longer than max_row, off
+ * not ascending from 0, a byte with bit 4 or 5 set.  m == 0: ORBHIP_OK.
+ * orbhip_map_kf_levels_missing: the keys of the live rows whose levels are missing or shorter than the row, ascending; *nout = their
+ * number, ORBHIP_E_CAPACITY when it exceeds cap (the first cap are written).  Host state only, no device work. */
+int orbhip_map_kf_levels(orbhip_ctx *ctx, int m, const uint64_t *kf_keys, const int32_t *off, const uint8_t *bytes);
+int orbhip_map_kf_levels_missing(orbhip_ctx *ctx, uint64_t *kf_keys_out, int cap, int *nout);
+/* orbhip_map_cull counts on the map as it is and applies nothing: culling a key frame changes the counts of every other one, so a
+ * caller that culls counts again for the candidates behind (ORB_SLAM2::LocalMapSearch::KeyFrameCulling does).  An entry resolves
+ * as above: live, not ORBHIP_MP_BAD, of the entry's generation.  For candidate k, entry i of its row resolving to point p, l its octave:
+ *   !monocular and the far bit set: the entry is skipped (the reference's continue).  Otherwise n_mps++.
+ *   obs(p)       = the sum of 1 + stereo bit over all resolving entries of all live rows that hold p, k's own included: Observations()
+ *   others(p, l) = the number of resolving entries of rows other than k that hold p with octave <= l + 1 (far and stereo bits play
+ *                  no part: the reference's inner loop tests neither)
+ *   the entry is redundant iff obs(p) > th_obs && others(p, l) >= th_obs; n_redundant counts those
+ *   redundant[k]      = (double)n_redundant > 0.9 * (double)n_mps, formed on the host: nRedundantObservations>0.9*nMPs
+ *   entry_state[k][i] (NULL to skip; [K][max_row], 0 beyond the row) 0 = not counted, 1 = counted, 2 = counted and redundant
+ * th_obs: the reference's 3.  A key twice gives the same answer twice.  K == 0: ORBHIP_OK.  Precondition for equality with the
+ * reference's loop over observation maps: every observer's row is in the table and current, flags are current (docs/parity.md).
+ * ORBHIP_E_ARG, checked before any device work, nothing written: a key the table does not know, th_obs < 1, K > 65536, any live
+ * row of the table (candidate or not) whose levels are missing.  ORBHIP_E_SIZE: more than 2^24 candidate row entries in one call.
+ * One upload (8 B per candidate), one result block, one synchronisation; scratch only grows.  Integer work: results are exact. */
+typedef struct orbhip_cull_count {
+    int32_t n_mps, n_redundant;
+} orbhip_cull_count;
+int orbhip_map_cull(orbhip_ctx *ctx, int K, const uint64_t *kf_keys, int monocular, int th_obs, orbhip_cull_count *counts /* [K] */,
+                    uint8_t *redundant /* [K] */, uint8_t *entry_state /* [K][max_row] or NULL */);
+
 /* ---- SearchByBoW against all candidate key frames in one call ----
  * Tracking::Relocalization (ref: src/Tracking.cc:2595-2616) and LoopClosing::ComputeSim3 (ref: src/LoopClosing.cc:304-332) call
  * ORBmatcher::SearchByBoW once per candidate key frame.  Here one call matches the fixed side against K candidates: every key frame

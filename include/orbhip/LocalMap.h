@@ -223,6 +223,56 @@ public:
     struct BowCandWays { long device, host; };
     static BowCandWays &BowCandCounts() { static BowCandWays w = {0, 0}; return w; }
 
+    // ---- LocalMapping::KeyFrameCulling on the resident map (orbhip_map_kf_levels, orbhip_map_cull; DESIGN.md section 22,
+    // INTEGRATION.md section 3e) ----
+    // The counting loop of KeyFrameCulling and KeyFrameCullingForMonoVI (ref: src/LocalMapping.cc:2705-2753, :1533-1581) for every
+    // key frame of vpKFs on the map as it is now: vCounts[k] = nMPs, nRedundantObservations and nRedundantObservations>0.9*nMPs of
+    // vpKFs[k].  One device call; before it, the octave / stereo / far byte of every feature (mvKeysUn, mvuRight, mvDepth against
+    // mThDepth) is uploaded, once per key frame, for the rows that have none yet.  A batch is not the sequence: SetBadFlag of one
+    // key frame changes Observations() of its points and can turn them bad, so these counts hold until the first cull and no longer
+    // (KeyFrameCulling below counts again).  A key frame without a row is put.  Precondition as UpdateConnections': every observer's
+    // row is in the table and current, flags are current.  A key frame that holds a non-NULL, non-bad point the store does not know,
+    // or that is bad itself, goes the host way: the reference's loop on the objects.  false = nothing filled (a device error,
+    // reported through hipdetail::Fail).
+    struct CullCount { int nMPs, nRedundant; bool bRedundant; };
+    bool CullCounts(const std::vector<KeyFrame *> &vpKFs, bool bMonocular, std::vector<CullCount> &vCounts);
+    // after the caller's pKF->SetBadFlag(): EraseKeyFrame(pKF), and one UpdateFlags upload for those of vpItsPoints (the key
+    // frame's GetMapPointMatches() from before the call) that are bad now
+    void KeyFrameCulled(KeyFrame *pKF, const std::vector<MapPoint *> &vpItsPoints);
+    // The whole loop over vpLocalKeyFrames, in the vector's order, with the reference's result: for every key frame but mnId == 0,
+    // skip(pKF) is asked at that moment (the VI variant's tests read GetPrevKeyFrame() / GetNextKeyFrame(), which an earlier cull
+    // relinks); a redundant one is culled through cull(pKF) -- the caller's pKF->SetBadFlag() -- and KeyFrameCulled, and the
+    // candidates behind it are counted again before the next verdict.  Device calls: culls + 1 at the most.  Returns the number
+    // culled; after a device error nothing more is culled.
+    template <class Skip, class Cull>
+    int KeyFrameCulling(const std::vector<KeyFrame *> &vpLocalKeyFrames, bool bMonocular, Skip skip, Cull cull)
+    {
+        std::vector<CullCount> vCounts;
+        size_t nFirst = 0;        // vCounts[i - nFirst] is vpLocalKeyFrames[i]'s
+        bool bCurrent = false;    // no cull since vCounts was made
+        int nCulled = 0;
+        for (size_t i = 0; i < vpLocalKeyFrames.size(); i++) {
+            KeyFrame *pKF = vpLocalKeyFrames[i];
+            if (pKF->mnId == 0) continue;
+            if (skip(pKF)) continue;
+            if (!bCurrent) {
+                if (!CullCounts(std::vector<KeyFrame *>(vpLocalKeyFrames.begin() + i, vpLocalKeyFrames.end()), bMonocular, vCounts)) return nCulled;
+                nFirst = i;
+                bCurrent = true;
+            }
+            if (!vCounts[i - nFirst].bRedundant) continue;
+            const std::vector<MapPoint *> vpItsPoints = pKF->GetMapPointMatches();
+            cull(pKF);
+            KeyFrameCulled(pKF, vpItsPoints);
+            bCurrent = false;
+            nCulled++;
+        }
+        return nCulled;
+    }
+    // how many key frames the CullCounts calls of this process sent each way (for the tests and tools/cull_latency.py)
+    struct CullWays { long device, host; };
+    static CullWays &CullWayCounts() { static CullWays w = {0, 0}; return w; }
+
     // orbhip_set_limit for this object's context: how many key-frame sets stay resident (4 .. 96; 96 from the first Fuse or
     // Refresh call on unless set here).  Returns the limit in force.
     int SetLimit(int maxSets);

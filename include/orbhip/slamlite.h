@@ -62,6 +62,10 @@ public:
     bool IsInKeyFrame(KeyFrame *pKF) { return mObservations.count(pKF) != 0; }
     int GetIndexInKeyFrame(KeyFrame *pKF) { return mObservations.count(pKF) ? (int)mObservations[pKF] : -1; }
     void AddObservation(KeyFrame *pKF, size_t idx);
+    // ref: src/MapPoint.cc:126-157 (body below KeyFrame): nObs goes down by 1, or by 2 for a stereo observation; mpRefKF, when it
+    // was pKF, becomes the remaining observer of lowest mnId (the reference takes the lowest heap address); at nObs <= 2 the
+    // reference's SetBadFlag follows: the flag, and EraseMapPointMatch in every remaining observer (the Map edit is not modelled)
+    void EraseObservation(KeyFrame *pKF);
     void Replace(MapPoint *pMP);
     MapPoint *GetReplaced() { return mpReplaced; }
     void SetDescriptor(const cv::Mat &d) { mDescriptor = d.clone(); }   // mDescriptor is protected in the reference
@@ -187,6 +191,19 @@ public:
     static long unsigned int &NextId() { static long unsigned int n = 0; return n; }
     bool isBad() { return mbBad; }                // ref: src/KeyFrame.cc (read by MapPoint::ComputeDistinctiveDescriptors)
     bool mbBad;
+    // The observation half of KeyFrame::SetBadFlag (ref: src/KeyFrame.cc:952-1040): EraseObservation on every point, then mbBad;
+    // mvpMapPoints stays as it is, as there; a key frame that is bad already returns at once, as there.  The edits of the covisibility graph, the spanning tree, the Map and the key-frame
+    // database, and the mbNotErase / mbToBeErased hand-over with LoopClosing, are not modelled.  Read by LocalMapping::KeyFrameCulling
+    // (ref: src/LocalMapping.cc:2692-2756): mvDepth (negative for monocular points) and mThDepth.
+    void SetBadFlag()
+    {
+        if (mbBad || mnId == 0) return;
+        for (size_t i = 0; i < mvpMapPoints.size(); i++)
+            if (mvpMapPoints[i]) mvpMapPoints[i]->EraseObservation(this);
+        mbBad = true;
+    }
+    std::vector<float> mvDepth;
+    float mThDepth = 0;
     std::vector<cv::KeyPoint> mvKeys, mvKeysUn;   // ref: include/KeyFrame.h (const members there)
     cv::Mat mDescriptors;
     DBoW2::FeatureVector mFeatVec;
@@ -304,6 +321,37 @@ inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx)
         nObs+=2;
     else
         nObs++;
+}
+
+inline void MapPoint::EraseObservation(KeyFrame *pKF)
+{
+    bool bBad = false;
+    if(mObservations.count(pKF))
+    {
+        const size_t idx = mObservations[pKF];
+        if(idx<pKF->mvuRight.size() && pKF->mvuRight[idx]>=0)
+            nObs-=2;
+        else
+            nObs--;
+        mObservations.erase(pKF);
+        if(mpRefKF==pKF)
+        {
+            mpRefKF = NULL;
+            for(std::map<KeyFrame *, size_t>::iterator mit=mObservations.begin(), mend=mObservations.end(); mit!=mend; mit++)
+                if(!mpRefKF || mit->first->mnId<mpRefKF->mnId)
+                    mpRefKF = mit->first;
+        }
+        if(nObs<=2)
+            bBad = true;
+    }
+    if(bBad)
+    {
+        const std::map<KeyFrame *, size_t> obs = mObservations;   // SetBadFlag of the reference (src/MapPoint.cc:165-183)
+        mObservations.clear();
+        mbBad = true;
+        for(std::map<KeyFrame *, size_t>::const_iterator mit=obs.begin(), mend=obs.end(); mit!=mend; mit++)
+            mit->first->EraseMapPointMatch(mit->second);
+    }
 }
 
 inline void MapPoint::Replace(MapPoint *pMP)

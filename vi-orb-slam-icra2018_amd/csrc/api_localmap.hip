@@ -401,6 +401,7 @@ static void kf_reset_table(OrbKfTable *K)
     for (int i = 0; i < K->maxKfs; i++) K->freeRows[i] = K->maxKfs - 1 - i;
     K->rowKey.assign(K->maxKfs, 0);
     K->entries.assign(K->maxKfs, std::vector<uint64_t>());
+    K->levelsN.assign(K->maxKfs, -1);
 }
 
 extern "C" int orbhip_map_kf_init(orbhip_ctx *c, int max_kfs, int max_row)
@@ -509,6 +510,7 @@ extern "C" int orbhip_map_kf_put(orbhip_ctx *c, uint64_t kf_key, int n, const ui
         K->freeRows.pop_back();
         K->rowOf.emplace(kf_key, row);
         K->rowKey[row] = kf_key;
+        K->levelsN[row] = -1;   // (another key's levels)
         K->rowHigh = std::max(K->rowHigh, row + 1);
     }
     K->entries[row].swap(ent);
@@ -639,6 +641,7 @@ extern "C" int orbhip_map_kf_erase(orbhip_ctx *c, uint64_t kf_key)
     if ((rc = kf_upload_row(c, K, row, std::vector<uint64_t>()))) return rc;   // the device forgets first
     K->entries[row].clear();
     K->rowKey[row] = 0;
+    K->levelsN[row] = -1;
     K->freeRows.push_back(row);
     K->rowOf.erase(it);
     return ORBHIP_OK;

@@ -1,5 +1,5 @@
 // localmap_store.h -- the host side of the resident map-point store and of the key-frame table, shared by the api_*.hip files
-// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip): device blocks, the key -> slot / key -> row
+// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip, api_cull.hip): device blocks, the key -> slot / key -> row
 // tables, what a call over several rows of the table (the ordered union) sets up, and the target records of the Fuse calls.
 #ifndef ORBHIP_LOCALMAP_STORE_H
 #define ORBHIP_LOCALMAP_STORE_H
@@ -25,6 +25,8 @@ struct OrbKfTable {
     std::vector<int32_t> freeRows;                         // (taken from the back: row 0 first)
     std::vector<uint64_t> rowKey;                          // [maxKfs] 0 = free
     std::vector<std::vector<uint64_t> > entries;           // [maxKfs] the row as uploaded: generation << 32 | slot, ~0 = no point
+    OrbBlock levels;                                       // u8 [maxKfs][maxRow], from the first orbhip_map_kf_levels on (api_cull.hip)
+    std::vector<int32_t> levelsN;                          // [maxKfs] features the row has levels for, -1 = none
 };
 
 struct OrbLocalMap {

@@ -576,6 +576,12 @@ int collect_blocks(uint32_t P);
 // k_covis.hip: qrows [nq] = the table rows of the queries, 32 to a pass (mark, count, clear); *nout zero on entry
 void launch_covis(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint32_t *mflags, int maxPoints,
                   uint32_t *marks, const int32_t *qrows, int nq, int capOut, int32_t *nout, void *trip);
+// k_cull.hip: cand [K] = {table row, row length}; *nids and tally [bound][17] zero on entry; counts [K] int2, state [K][maxRow] or null
+void launch_cull(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint8_t *levels, const uint32_t *mflags,
+                 int maxPoints, uint32_t *marks, const void *cand, int K, uint32_t bound, uint32_t *nids, uint32_t *tally, int monocular,
+                 int thObs, void *counts, uint8_t *state);
+// desc [m] = {table row, first byte, length}: the level bytes of m key frames into levels [maxKfs][maxRow]
+void launch_cull_levels(hipStream_t s, const uint8_t *bytes, const int32_t *desc, int m, int maxKfs, int maxRow, uint8_t *levels);
 void launch_collect(hipStream_t s, const void *rows, int nrows, int stride, const int32_t *rowIdx, const uint32_t *off, int nkf,
                     uint32_t P, const uint32_t *mflags, int maxPoints, const uint32_t *marks, uint32_t *first, int32_t *cand,
                     int32_t *blockCnt, int capOut, int32_t *slots, uint8_t *skip, int32_t *nlocal);

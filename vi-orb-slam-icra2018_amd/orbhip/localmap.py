@@ -49,6 +49,13 @@ def fuse_target(set_key, cam, inv_level_sigma2):
     return t
 
 
+def level_byte(octave, stereo, far):
+    """The level byte of one key-frame feature (orbhip_map_kf_levels): mvKeysUn[i].octave (0..15), mvuRight[i] >= 0,
+    mvDepth[i] > mThDepth || mvDepth[i] < 0."""
+    assert 0 <= int(octave) <= 15
+    return int(octave) | (0x40 if stereo else 0) | (0x80 if far else 0)
+
+
 def predict_scale_table(log_scale_factor, nlevels):
     """The threshold table of PredictScale (host only): T[k] = smallest float ratio whose level exceeds k."""
     t = np.zeros(max(nlevels - 1, 1), f32)
@@ -194,6 +201,46 @@ class LocalMap:
             a, b = int(off[q]), int(off[q + 1])
             out.append((nbr[a:b].copy(), w[a:b].copy(), nbr[a:b][order[a:a + nord[q]]].copy()))
         return out
+
+    # ---- the counts of KeyFrameCulling ----
+    def kf_levels(self, kf_keys, rows_of_bytes, off=None):
+        """orbhip_map_kf_levels: one level byte (level_byte()) per feature of every key frame of kf_keys, in one upload.  off: the
+        offsets to pass instead of those of the rows' lengths (for the tests of the call's checks)."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        rows = [np.ascontiguousarray(r, np.uint8).ravel() for r in rows_of_bytes]
+        assert len(rows) == len(kk)
+        if off is None:
+            off = np.zeros(len(kk) + 1, np.int32)
+            off[1:] = np.cumsum([len(r) for r in rows])
+        off = np.ascontiguousarray(off, np.int32)
+        assert len(off) == len(kk) + 1
+        b = np.concatenate(rows + [np.zeros(1, np.uint8)])
+        check(self._L.orbhip_map_kf_levels(self._ctx.handle, len(kk), _p(kk), _p(off), _p(b)), self._ctx.handle, "orbhip_map_kf_levels")
+
+    def kf_levels_missing(self):
+        """The keys of the live rows whose levels are missing or shorter than the row, ascending."""
+        cap = self.kf_info()[1]
+        out, n = np.zeros(max(cap, 1), np.uint64), C.c_int()
+        check(self._L.orbhip_map_kf_levels_missing(self._ctx.handle, _p(out), cap, C.byref(n)), self._ctx.handle,
+              "orbhip_map_kf_levels_missing")
+        return out[:n.value].copy()
+
+    def cull(self, kf_keys, monocular, th_obs=3, want_entries=False):
+        """orbhip_map_cull: (counts [K][2] = n_mps, n_redundant; redundant [K] bool) for the candidates kf_keys on the map as it is,
+        and with want_entries entry_state [K][max_row] behind them.  The buffers start as -7 / 77 so that a caller sees what a failed
+        call left alone (e.outputs)."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        K = len(kk)
+        counts, red = np.full((max(K, 1), 2), -7, np.int32), np.full(max(K, 1), 77, np.uint8)
+        st = np.full((max(K, 1), self.kf_info()[2]), 77, np.uint8) if want_entries else None
+        try:
+            check(self._L.orbhip_map_cull(self._ctx.handle, K, _p(kk), int(bool(monocular)), th_obs, _p(counts), _p(red), _p(st)),
+                  self._ctx.handle, "orbhip_map_cull")
+        except capi.OrbHipError as e:
+            e.outputs = (counts, red, st)
+            raise
+        out = (counts[:K].copy(), red[:K].astype(bool))
+        return out + (st[:K].copy(),) if want_entries else out
 
     def search_by_bow_candidates(self, mode, fixed_set_key, fixed_row_key, n_fixed, candidates, th=50, nnratio=0.75, check_ori=True,
                                  gather=None, cap=None):

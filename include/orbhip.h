@@ -983,6 +983,54 @@ int orbhip_map_refresh(orbhip_ctx *ctx, const orbhip_refresh_params *prm, int nk
 int orbhip_map_get(orbhip_ctx *ctx, int n, const uint64_t *keys, float *pos, float *normal, float *min_dist, float *max_dist,
                    uint8_t *desc, uint8_t *flags);
 
+/* ---- map points moved in place on the resident store ----
+ * orbhip_map_correct_sim3: the point loop of LoopClosing::CorrectLoop (ref: src/LoopClosing.cc:523-568) for the points of K corrected
+ * key frames.  Per point that is not ORBHIP_MP_BAD in the store: the store's position, widened to double, goes through
+ * xf[corr].Siw and then xf[corr].corrected_Swi (g2o::Sim3::map, s*(r*xyz)+t, every operation rounded on its own; docs/parity.md,
+ * "CorrectLoop"), is rounded to float once and written back (status bit 0).  A point with a non-empty list then gets
+ * MapPoint::UpdateNormalAndDepth as orbhip_map_refresh computes it (status bit 1), with the camera centre of observer o taken as
+ * kfs[o].Ow_after when 0 <= kfs[o].rank < corr[p] and as kfs[o].Ow_before otherwise: in the reference the points of key frame j are
+ * refreshed after SetPose of key frames 0 .. j - 1 and before its own.  The same rule gives the reference observer's centre.
+ *   prm          scale_factors, nlevels as for orbhip_map_refresh; what is ignored
+ *   xf [K]       per corrected key frame, in the loop's order; kfs [nkf] the key frames the lists name, rank = position in that
+ *                order or -1 for a key frame that is not corrected
+ *   point_keys [P]; corr [P] in [0, K); off [P + 1] ascending from 0; obs_kf [off[P]] into kfs, each list in ascending KeyFrame::mnId;
+ *   ref_pos [P]  position of mpRefKF in the list; ref_level [P] the octave of mpRefKF's feature.  No feature set has to be resident.
+ *   status [P]; pos_out, normal_out [3 P], min_dist_out, max_dist_out [P]: the store's values after the call.  Any output but
+ *   status may be NULL.  A bad point keeps everything (status 0); an empty list moves the position only (status 1).  Flags,
+ *   generation and descriptor are never touched.
+ *   ORBHIP_E_ARG, checked before any device work, nothing changed: an unknown point key or a key twice; corr, obs_kf out of range;
+ *   ref_pos outside a non-empty list; ref_level >= nlevels; nlevels outside 1..16; off not ascending from 0; a rank outside [-1, K);
+ *   a non-negative rank twice; K < 1 with P > 0.  ORBHIP_E_SIZE: a list of 2^20 rows or more.  P == 0: ORBHIP_OK.
+ *   One packed upload (128 B per corrected key frame, 28 B per listed key frame, 17 B per point, 4 B per observation), one launch,
+ *   one result block, one synchronisation.
+ * orbhip_map_correct_se3: the point loop of LoopClosing::RunGlobalBundleAdjustment (ref: :762-797).  corr[p] >= 0: Xc =
+ *   Rcw_before*Xw + tcw_before, Xw' = Rwc*Xc + twc of xf[corr[p]], each one gemm (products and sums in double from 0.0, t added, one
+ *   rounding to float); corr[p] == -1: the position becomes pos_set[3 p] (SetWorldPos(mPosGBA)).  Position only: status bit 0.  Bad
+ *   points are untouched, status 0.  ORBHIP_E_ARG: an unknown point key or a key twice; corr outside [-1, K); K < 0; a corr of -1
+ *   with pos_set == NULL.  pos_out [3 P] may be NULL. */
+typedef struct {
+    double q[4]; /* x y z w, unit */
+    double t[3];
+    double s;
+} orbhip_sim3d;
+typedef struct {
+    orbhip_sim3d Siw, corrected_Swi;
+} orbhip_correct_xf;
+typedef struct {
+    float Ow_before[3], Ow_after[3];
+    int32_t rank;
+} orbhip_correct_kf;
+typedef struct {
+    float Rcw_before[9], tcw_before[3], Rwc[9], twc[3];
+} orbhip_correct_se3;
+int orbhip_map_correct_sim3(orbhip_ctx *ctx, const orbhip_refresh_params *prm, int K, const orbhip_correct_xf *xf, int nkf,
+                            const orbhip_correct_kf *kfs, int P, const uint64_t *point_keys, const int32_t *corr, const int32_t *off,
+                            const int32_t *obs_kf, const int32_t *ref_pos, const uint8_t *ref_level, uint8_t *status, float *pos_out,
+                            float *normal_out, float *min_dist_out, float *max_dist_out);
+int orbhip_map_correct_se3(orbhip_ctx *ctx, int K, const orbhip_correct_se3 *xf, int P, const uint64_t *point_keys, const int32_t *corr,
+                           const float *pos_set, uint8_t *status, float *pos_out);
+
 /* ---- the covisibility graph from the resident key-frame table ----
  * KeyFrame::UpdateConnections (ref: src/KeyFrame.cc:731-812) for a batch of key frames.  w(q, j) = the number of points that are
  * resolving entries (live, not ORBHIP_MP_BAD, of the entry's generation) of both row q and row j of the table above.

@@ -156,7 +156,8 @@ public:
     // reference walks a map<KeyFrame*, ...> by heap address; docs/parity.md).  All targets are projected and searched in one
     // device call (64 at a time beyond that); the results are applied target by target, re-reading isBad(), GetMapPoints() and
     // what the feature holds at that moment, and a loop point whose descriptor changed because it survived a Replace in an
-    // earlier target is searched again before a later target is applied.  Points that CorrectLoop moved must have been Put.
+    // earlier target is searched again before a later target is applied.  Points that CorrectLoop moved must be current in the
+    // store: CorrectLoopPoints below leaves them so.
     void SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::Mat> > &vCorrectedPoses, const std::vector<MapPoint *> &vpLoopMapPoints,
                        float th = 4);
     // where SearchAndFuse spends its time, in microseconds, summed over the calls since the caller last zeroed it
@@ -272,6 +273,38 @@ public:
     // how many key frames the CullCounts calls of this process sent each way (for the tests and tools/cull_latency.py)
     struct CullWays { long device, host; };
     static CullWays &CullWayCounts() { static CullWays w = {0, 0}; return w; }
+
+    // ---- map points moved in place on the resident store (orbhip_map_correct_sim3, orbhip_map_correct_se3; DESIGN.md section 23,
+    // INTEGRATION.md section 3e) ----
+    // A g2o::Sim3 as the call reads it: rotation().coeffs() (x y z w), translation(), scale().  The Sim3 algebra -- the composition
+    // g2oSic*mg2oScw, inverse(), the quaternion from Riw -- stays with the caller, who holds the g2o objects.
+    struct Sim3d { double q[4], t[3], s; };
+    // one iteration of CorrectLoop's loop over CorrectedSim3: the key frame, NonCorrectedSim3[pKF], CorrectedSim3[pKF].inverse() and
+    // the pose the loop sets at its end (Converter::toCvSE3(eigR, eigt/s))
+    struct LoopCorrection { KeyFrame *pKF; Sim3d Siw, correctedSwi; cv::Mat correctedTiw; };
+    // The point loop and the SetPose of LoopClosing::CorrectLoop (ref: src/LoopClosing.cc:523-564) as one device call.  The vector's
+    // order stands for the iteration order of the reference's map<KeyFrame*, g2o::Sim3> (docs/parity.md).  Every key frame's
+    // GetMapPointMatches() is walked in order; NULL entries, bad points and points already stamped with nCurrentKFid are skipped, so
+    // the first key frame to reach a point owns it.  A point is stamped (mnCorrectedByKF, mnCorrectedReference), mapped through Siw
+    // and correctedSwi in double and refreshed as MapPoint::UpdateNormalAndDepth would at that moment of the sequence: observers
+    // earlier in the vector stand at their corrected centres, the others where they stood.  Position, normal and distance range are
+    // assigned to the objects from what the call wrote into the store; then SetPose(correctedTiw) runs on every key frame in order.
+    // A point that was never Put, or whose mpRefKF is not among its observers, goes the host way at its turn in the sequence and is
+    // Put afterwards.  pKF->UpdateConnections() stays with the caller (UpdateConnections above).  Returns the number of points moved.
+    int CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsigned long nCurrentKFid);
+    // The point loop of LoopClosing::RunGlobalBundleAdjustment (ref: :765-797) over vpMPs (Map::GetAllMapPoints(): each point once;
+    // NULL entries, bad points and second occurrences are skipped), after the caller has set mTcwBefGBA and the new pose of every
+    // adjusted key frame: a point with mnBAGlobalForKF == nLoopKF takes mPosGBA, another is carried from its reference key frame's
+    // mTcwBefGBA to its GetPoseInverse(); a point whose reference key frame was not adjusted is left alone.  One device call; the
+    // positions are assigned to the objects.  A point that was never Put goes the host way and is Put.  Returns the number moved.
+    int ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned long nLoopKF);
+    // how many points the two calls of this process sent each way (for the tests and tools/correct_latency.py)
+    struct CorrectWays { long device, host; };
+    static CorrectWays &CorrectCounts() { static CorrectWays w = {0, 0}; return w; }
+    // where the two calls spend their time, in microseconds, summed since the caller last zeroed it (tools/correct_latency.py):
+    // building the lists, the entry point, assigning the results (with the host way and SetPose)
+    struct CorrectPhases { double prepare, device, apply; };
+    static CorrectPhases &CorrectTimes() { static CorrectPhases p = {0, 0, 0}; return p; }
 
     // orbhip_set_limit for this object's context: how many key-frame sets stay resident (4 .. 96; 96 from the first Fuse or
     // Refresh call on unless set here).  Returns the limit in force.

@@ -48,6 +48,7 @@ public:
     int Observations() { return nObs; }
     cv::Mat GetDescriptor() { return mDescriptor.clone(); }
     cv::Mat GetWorldPos() { return mWorldPos.clone(); }
+    void SetWorldPos(const cv::Mat &Pos) { mWorldPos = Pos.clone(); }   // ref: src/MapPoint.cc:75-80
     float GetMinDistanceInvariance() { return 0.8f*mfMinDistance; }   // ref: src/MapPoint.cc:388-398
     float GetMaxDistanceInvariance() { return 1.2f*mfMaxDistance; }
     int PredictScale(const float &currentDist, Frame *pF);           // ref: src/MapPoint.cc:417-432 (body below Frame)
@@ -80,6 +81,13 @@ public:
     // observations are walked in ascending KeyFrame::mnId.  Nothing happens while mpRefKF is NULL.
     void UpdateNormalAndDepth();
     KeyFrame *mpRefKF = 0;                   // ref: include/MapPoint.h (protected there)
+    KeyFrame *GetReferenceKeyFrame() { return mpRefKF; }
+    // Variables used by loop closing (ref: include/MapPoint.h:113-117): the stamps LoopClosing::CorrectLoop leaves on a point it
+    // moved, and what RunGlobalBundleAdjustment reads (LocalMapSearch::CorrectLoopPoints / ApplyGlobalBA)
+    long unsigned int mnCorrectedByKF = 0;
+    long unsigned int mnCorrectedReference = 0;
+    cv::Mat mPosGBA;                         // 3 x 1 CV_32F
+    long unsigned int mnBAGlobalForKF = 0;
     static bool &RecomputeOnReplace() { static bool b = false; return b; }
 
     // ref: include/MapPoint.h "long unsigned int mnId; static long unsigned int nNextId;": mnId + 1 is the key under which
@@ -240,6 +248,35 @@ public:
         return t;
     }
     cv::Mat GetCameraCenter() { return Ow.clone(); }
+    // ref: src/KeyFrame.cc:95-118, :120-130.  Ow = -Rcw.t()*tcw is one gemm with alpha = -1: products summed in double, one
+    // rounding (as host/MatcherDetail.h decompose_sim3 writes it); Twc = [Rcw.t() | Ow]
+    void SetPose(const cv::Mat &Tcw_)
+    {
+        Tcw = Tcw_.clone();
+        cv::Mat O(3, 1, CV_32F);
+        for (int r = 0; r < 3; r++) {
+            double s = 0;
+            for (int k = 0; k < 3; k++) s += (double)Tcw.at<float>(k, r) * (double)Tcw.at<float>(k, 3);
+            O.at<float>(r, 0) = (float)(-1.0 * s + 0.0);
+        }
+        Ow = O;
+    }
+    cv::Mat GetPose() { return Tcw.clone(); }
+    cv::Mat GetPoseInverse()
+    {
+        cv::Mat Twc = cv::Mat::zeros(4, 4, CV_32F);
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) Twc.at<float>(r, c) = Tcw.at<float>(c, r);
+            Twc.at<float>(r, 3) = Ow.at<float>(r, 0);
+        }
+        Twc.at<float>(3, 3) = 1.f;
+        return Twc;
+    }
+    // Variables used by loop closing (ref: include/KeyFrame.h:188-191): the pose before a global bundle adjustment and the stamp
+    // of the adjustment that moved the key frame, read by LocalMapSearch::ApplyGlobalBA
+    cv::Mat mTcwGBA;
+    cv::Mat mTcwBefGBA;
+    long unsigned int mnBAGlobalForKF = 0;
     cv::Mat Tcw;                                  // 4 x 4 CV_32F (protected in the reference; the test programs fill it)
     cv::Mat Ow;                                   // 3 x 1 CV_32F
 

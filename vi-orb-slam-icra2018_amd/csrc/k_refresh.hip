@@ -11,15 +11,7 @@
 //                   writing inside the launch is safe.
 //   k_map_gather    store entries by slot into one result block (orbhip_map_get).
 // Every float / double operation is individually rounded (docs/parity.md, "UpdateNormalAndDepth").
-#include "localmap_dev.h"
-
-// cv::norm(NORM_L2) of a CV_32F 3-vector: squares summed in double, the root in double
-__device__ __forceinline__ double norm3(float x, float y, float z)
-{
-    double sq = __dadd_rn(__dmul_rn((double)x, (double)x), __dmul_rn((double)y, (double)y));
-    sq = __dadd_rn(sq, __dmul_rn((double)z, (double)z));
-    return __dsqrt_rn(sq);
-}
+#include "refresh_dev.h"   // the normal half: normal_and_depth, shared with k_correct.hip
 
 __global__ __launch_bounds__(256) void k_map_refresh(const RefreshKfDev *__restrict__ kfs, const orbhip_refresh_params *__restrict__ prm,
                                                      const int32_t *__restrict__ slots, const int32_t *__restrict__ off,
@@ -84,32 +76,14 @@ __global__ __launch_bounds__(256) void k_map_refresh(const RefreshKfDev *__restr
     }
 
     if (live && (what & ORBHIP_REFRESH_NORMAL)) {
-        float nx = 0.f, ny = 0.f, nz = 0.f;
-        for (int i0 = 0; i0 < N; i0 += 16) {
-            const int i = i0 + lane;
-            float tx = 0.f, ty = 0.f, tz = 0.f;
-            if (i < N) {
-                const RefreshKfDev &K = kfs[obs[s + i].x];
-                const float dx = __fsub_rn(A.x, K.ox), dy = __fsub_rn(A.y, K.oy), dz = __fsub_rn(A.z, K.oz);
-                const float a = (float)__ddiv_rn(1.0, norm3(dx, dy, dz));   // normali / norm: a MatExpr scaled by 1.0 / norm
-                tx = __fmul_rn(dx, a), ty = __fmul_rn(dy, a), tz = __fmul_rn(dz, a);
-            }
-            const int m = min(16, N - i0);
-            for (int jj = 0; jj < m; jj++) {   // normal = normal + alpha * normali, in list order
-                nx = __fadd_rn(__shfl(tx, jj, 16), nx);
-                ny = __fadd_rn(__shfl(ty, jj, 16), ny);
-                nz = __fadd_rn(__shfl(tz, jj, 16), nz);
-            }
-        }
-        const float invN = (float)__ddiv_rn(1.0, (double)N);
         const int2 orf = obs[s + min(max(refPos[p], 0), N - 1)];
-        const RefreshKfDev &R = kfs[orf.x];
-        const float dist = (float)norm3(__fsub_rn(A.x, R.ox), __fsub_rn(A.y, R.oy), __fsub_rn(A.z, R.oz));
-        const int level = min(max(R.kps[orf.y].octave, 0), ORBHIP_MAX_LEVELS - 1);
-        const int top = min(max(prm->nlevels - 1, 0), ORBHIP_MAX_LEVELS - 1);
-        B.x = __fmul_rn(nx, invN), B.y = __fmul_rn(ny, invN), B.z = __fmul_rn(nz, invN);
-        B.w = __fmul_rn(dist, prm->scale_factors[level]);
-        minDist = __fdiv_rn(B.w, prm->scale_factors[top]);
+        const int level = kfs[orf.x].kps[orf.y].octave;
+        normal_and_depth(A.x, A.y, A.z, N, lane, refPos[p], level, prm,
+                         [&](int j, float &ox, float &oy, float &oz) {   // the observer's centre: the one of the call's table
+                             const RefreshKfDev &K = kfs[obs[s + j].x];
+                             ox = K.ox, oy = K.oy, oz = K.oz;
+                         },
+                         B, minDist);
         st |= ORBHIP_REFRESH_NORMAL;
     }
 

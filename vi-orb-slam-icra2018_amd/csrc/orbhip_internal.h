@@ -539,6 +539,13 @@ void launch_map_refresh(hipStream_t s, const RefreshKfDev *kfs, const orbhip_ref
                         float *minOut);
 void launch_map_gather(hipStream_t s, const int32_t *slots, int n, int maxPoints, const void *geoA, const void *geoB,
                        const uint32_t *mflags, const void *mdesc, void *aOut, void *bOut, void *descOut, uint32_t *flagsOut);
+// k_correct.hip
+void launch_map_correct_sim3(hipStream_t s, const orbhip_correct_xf *xf, const orbhip_correct_kf *kfs, const orbhip_refresh_params *prm,
+                             const int32_t *slots, const int32_t *corr, const int32_t *off, const int32_t *obs, const int32_t *refPos,
+                             const uint8_t *refLevel, int P, int K, int maxPoints, void *geoA, void *geoB, const uint32_t *mflags,
+                             uint8_t *status, void *geoAOut, void *geoBOut);
+void launch_map_correct_se3(hipStream_t s, const orbhip_correct_se3 *xf, const int32_t *slots, const int32_t *corr, const float *posSet,
+                            int P, int K, int maxPoints, void *geoA, const uint32_t *mflags, uint8_t *status, float *posOut);
 // k_projtrack.hip
 void launch_project_last_frame(hipStream_t s, const void *geoA, const uint32_t *mflags, int maxPoints, const orbhip_local_camera *cams,
                                const int32_t *slots, const orbhip_keypoint *lastKps, const int32_t *motion, const int32_t *nq, int capQ,

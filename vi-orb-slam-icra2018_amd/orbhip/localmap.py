@@ -22,7 +22,11 @@ FUSE_TARGET_DTYPE = np.dtype([("set_key", "<u8"), ("cam", CAMERA_DTYPE), ("inv_l
 REFRESH_DESC, REFRESH_NORMAL, KF_BAD = 1, 2, 1
 REFRESH_KF_DTYPE = np.dtype([("set_key", "<u8"), ("Ow", "<f4", 3), ("flags", "<u4")])   # orbhip_refresh_kf
 REFRESH_PARAMS_DTYPE = np.dtype([("scale_factors", "<f4", 16), ("nlevels", "<i4"), ("what", "<i4")])   # orbhip_refresh_params
-POINT_DTYPE = np.dtype([("u", "<f4"), ("v", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
+SIM3D_DTYPE = np.dtype([("q", "<f8", 4), ("t", "<f8", 3), ("s", "<f8")])   # orbhip_sim3d: q = x y z w
+CORRECT_XF_DTYPE = np.dtype([("Siw", SIM3D_DTYPE), ("corrected_Swi", SIM3D_DTYPE)])   # orbhip_correct_xf
+CORRECT_KF_DTYPE = np.dtype([("Ow_before", "<f4", 3), ("Ow_after", "<f4", 3), ("rank", "<i4")])   # orbhip_correct_kf
+CORRECT_SE3_DTYPE = np.dtype([("Rcw_before", "<f4", 9), ("tcw_before", "<f4", 3), ("Rwc", "<f4", 9), ("twc", "<f4", 3)])   # orbhip_correct_se3
+POINT_DTYPE =np.dtype([("u", "<f4"), ("v", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
                         ("in_view", "<i4")])     # orbhip_local_point
 
 
@@ -446,6 +450,45 @@ class LocalMap:
         args = [_p(bufs[k]) if k in want else None for k in ("pos", "normal", "min_dist", "max_dist", "desc", "flags")]
         check(self._L.orbhip_map_get(self._ctx.handle, n, _p(keys), *args), self._ctx.handle, "orbhip_map_get")
         return {k: bufs[k][:n].copy() for k in want}
+
+    # ---- map points moved in place: CorrectLoop's Sim3 pass and the global-BA update ----
+    def map_correct_sim3(self, scale_factors, nlevels, xf, kfs, point_keys, corr, off, obs_kf, ref_pos, ref_level, want=True):
+        """orbhip_map_correct_sim3.  xf: CORRECT_XF_DTYPE records in the loop's order; kfs: CORRECT_KF_DTYPE records; corr [P]; the lists
+        as CSR (off [P + 1], obs_kf [off[P]]) in ascending KeyFrame::mnId; ref_pos, ref_level [P].  Returns (status, pos, normal,
+        min_dist, max_dist); with want=False every output but status is passed as NULL and comes back None."""
+        prm = np.zeros(1, REFRESH_PARAMS_DTYPE)
+        sf = np.asarray(scale_factors, f32)
+        prm["scale_factors"][0][:len(sf)] = sf[:16]
+        prm["nlevels"] = nlevels
+        xf = np.ascontiguousarray(xf, CORRECT_XF_DTYPE)
+        kfs = np.ascontiguousarray(kfs, CORRECT_KF_DTYPE)
+        pk = np.ascontiguousarray(point_keys, np.uint64).ravel()
+        co, off = np.ascontiguousarray(corr, np.int32).ravel(), np.ascontiguousarray(off, np.int32).ravel()
+        ok, rp = np.ascontiguousarray(obs_kf, np.int32).ravel(), np.ascontiguousarray(ref_pos, np.int32).ravel()
+        rl = np.ascontiguousarray(ref_level, np.uint8).ravel()
+        P = len(pk)
+        assert len(off) == P + 1 and len(rp) == P and len(co) == P and len(rl) == P
+        m = max(P, 1)
+        status = np.zeros(m, np.uint8)
+        outs = [np.zeros((m, 3), f32), np.zeros((m, 3), f32), np.zeros(m, f32), np.zeros(m, f32)] if want else [None] * 4
+        check(self._L.orbhip_map_correct_sim3(self._ctx.handle, _p(prm), len(xf), _p(xf), len(kfs), _p(kfs), P, _p(pk), _p(co), _p(off), _p(ok),
+                                              _p(rp), _p(rl), _p(status), *[_p(x) for x in outs]), self._ctx.handle, "orbhip_map_correct_sim3")
+        return (status[:P].copy(),) + tuple(None if x is None else x[:P].copy() for x in outs)
+
+    def map_correct_se3(self, xf, point_keys, corr, pos_set=None, want=True):
+        """orbhip_map_correct_se3.  xf: CORRECT_SE3_DTYPE records; corr [P] in [0, K) or -1 = take pos_set [P][3].  Returns (status, pos)."""
+        xf = np.ascontiguousarray(xf, CORRECT_SE3_DTYPE)
+        pk = np.ascontiguousarray(point_keys, np.uint64).ravel()
+        co = np.ascontiguousarray(corr, np.int32).ravel()
+        ps = None if pos_set is None else np.ascontiguousarray(pos_set, f32).reshape(-1, 3)
+        P = len(pk)
+        assert len(co) == P and (ps is None or len(ps) == P)
+        m = max(P, 1)
+        status = np.zeros(m, np.uint8)
+        pos = np.zeros((m, 3), f32) if want else None
+        check(self._L.orbhip_map_correct_se3(self._ctx.handle, len(xf), _p(xf), P, _p(pk), _p(co), _p(ps), _p(status), _p(pos)),
+              self._ctx.handle, "orbhip_map_correct_se3")
+        return status[:P].copy(), (None if pos is None else pos[:P].copy())
 
     def search_last_frame_device(self, d_kps, d_desc, d_counts, cap, B, d_u_right, d_occupied, gp, d_cell_off, d_cell_idx, d_cam, d_slots,
                                  d_last_kps, d_motion, d_nq, cap_q, check_ori, th_high, d_queries, d_n_active, d_match, d_nmatches):

@@ -570,8 +570,9 @@ int orbhip_debug_roundtrip(orbhip_ctx *ctx, int mode, int iters, double *us_per_
  * 5 k_quadtree (tables in LDS), 6 k_quadtree (tables and candidates in LDS, a frame or two), 7 k_quadtree (tables in global
  * memory), 8 k_bow_lane, 9 k_bow_seq (descriptors in LDS), 10 k_bow_seq (descriptors in global memory), 11 k_fast_fix on the
  * tall-cell instance, 12 k_describe, 13 k_describe_blur, 14 k_blur, 15 k_tri_match_sets with a node of at most 128 side-2
- * features (held in registers), 16 k_tri_match_sets with a node of more than 128 (strided).  Returns the mask; reset != 0
- * clears it. */
+ * features (held in registers), 16 k_tri_match_sets with a node of more than 128 (strided), 17 k_grid_build (cell entries sorted
+ * in LDS, 1024 threads: fewer than 8 frames), 18 k_grid_build (LDS, 256 threads: 8 frames or more), 19 k_grid_build (cell
+ * entries sorted in place in global memory: more than 12288 slots per frame).  Returns the mask; reset != 0 clears it. */
 unsigned orbhip_debug_path_mask(int reset);
 
 /* ---- multi-GPU (one process per GPU) ----

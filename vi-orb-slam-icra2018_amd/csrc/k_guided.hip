@@ -1447,17 +1447,19 @@ int launch_grid_build(hipStream_t s, const orbhip_keypoint *kps, const int32_t *
                       float minY, float invW, float invH, int32_t *cellOff, int32_t *cellIdx, int32_t *cellOff2, int32_t *cellIdx2)
 {
     const GridParams gp = {minX, minY, invW, invH};
-    if ((size_t)cap * 4 <= 48 * 1024)
+    if ((size_t)cap * 4 <= 48 * 1024) {
         if (B < 8)
             hipLaunchKernelGGL((k_grid_build<true, 1024>), dim3(B, 1, 1), dim3(1024, 1, 1), (size_t)cap * 4, s, kps, cnt, cap, gp, cellOff,
                                cellIdx, cellOff2, cellIdx2);
         else
             hipLaunchKernelGGL((k_grid_build<true, 256>), dim3(B, 1, 1), dim3(256, 1, 1), (size_t)cap * 4, s, kps, cnt, cap, gp, cellOff,
                                cellIdx, cellOff2, cellIdx2);
-    else {
+        orb_path(B < 8 ? ORB_PATH_GRID_LDS1024 : ORB_PATH_GRID_LDS256);
+    } else {
         if (cellOff2 || cellIdx2) return ORBHIP_E_SIZE;   // (the twin is written by the LDS form)
         hipLaunchKernelGGL((k_grid_build<false, 256>), dim3(B, 1, 1), dim3(256, 1, 1), 0, s, kps, cnt, cap, gp, cellOff, cellIdx,
                            (int32_t *)nullptr, (int32_t *)nullptr);
+        orb_path(ORB_PATH_GRID_GLOBAL);
     }
     return ORBHIP_OK;
 }

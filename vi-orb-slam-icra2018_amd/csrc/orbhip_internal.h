@@ -49,7 +49,8 @@ enum OrbPath : unsigned {
     ORB_PATH_FAST_FIX = 1u << 0, ORB_PATH_FAST_GENERIC = 1u << 1, ORB_PATH_RESIZE_FIT = 1u << 2, ORB_PATH_RESIZE_TILES = 1u << 3,
     ORB_PATH_PYRAMID_CHAIN = 1u << 4, ORB_PATH_QT_LDS = 1u << 5, ORB_PATH_QT_LDSPTS = 1u << 6, ORB_PATH_QT_GLOBAL = 1u << 7,
     ORB_PATH_BOW_LANE = 1u << 8, ORB_PATH_BOW_SEQ_LDS = 1u << 9, ORB_PATH_BOW_SEQ_GLOBAL = 1u << 10, ORB_PATH_FAST_TALL = 1u << 11, ORB_PATH_DESCRIBE = 1u << 12, ORB_PATH_DESCRIBE_BLUR = 1u << 13, ORB_PATH_BLUR = 1u << 14,
-    ORB_PATH_TRI_SETS_REG = 1u << 15, ORB_PATH_TRI_SETS_STRIDED = 1u << 16
+    ORB_PATH_TRI_SETS_REG = 1u << 15, ORB_PATH_TRI_SETS_STRIDED = 1u << 16,
+    ORB_PATH_GRID_LDS1024 = 1u << 17, ORB_PATH_GRID_LDS256 = 1u << 18, ORB_PATH_GRID_GLOBAL = 1u << 19
 };
 extern std::atomic<unsigned> g_orbPathMask;
 static inline void orb_path(unsigned bit) { g_orbPathMask.fetch_or(bit, std::memory_order_relaxed); }

@@ -1086,6 +1086,36 @@ typedef struct orbhip_cull_count {
 int orbhip_map_cull(orbhip_ctx *ctx, int K, const uint64_t *kf_keys, int monocular, int th_obs, orbhip_cull_count *counts /* [K] */,
                     uint8_t *redundant /* [K] */, uint8_t *entry_state /* [K][max_row] or NULL */);
 
+/* ---- the structure of local bundle adjustment's problem from the resident key-frame table ----
+ * Optimizer::LocalBundleAdjustment (ref: src/Optimizer.cc:2763-2960; the windowed forms at :980 ff. and :1720 ff., BundleAdjustment
+ * at :2358 ff. over the whole map) forms, before the solver sees a vertex, lLocalMapPoints from the local key frames' mvpMapPoints,
+ * lFixedCameras from every local point's observation map, and one edge per observation.  All three are functions of the rows.
+ * An entry resolves as above: live, not ORBHIP_MP_BAD, of the entry's generation.
+ *   kf_keys [nkf]          the local key frames in the caller's order, nkf <= 65536; the second copy of a key adds nothing
+ *   point_keys_out [0 .. *npoints)   exactly what orbhip_map_collect returns for the same kf_keys, element for element
+ *   edge_off_out [*npoints + 1], edges_out [*nedges]: the observers of point j are edges_out[edge_off_out[j] .. edge_off_out[j + 1]),
+ *                          one per resolving entry of ANY live row of the table that names the point, in ascending key-frame key
+ *                          (the canonical stand-in for map<KeyFrame*, size_t>'s order by address, docs/parity.md).  Every point
+ *                          has at least one edge; edge_off_out[*npoints] == *nedges.
+ *   edges_out[e].kf        < nkf: the observer is kf_keys[kf], the key's first occurrence; otherwise fixed_keys_out[kf - nkf]
+ *   edges_out[e].idx       the feature index in that key frame's row
+ *   fixed_keys_out [0 .. *nfixed)    the observers that are no local key frame, each once, in the order of their first edge in
+ *                          edges_out: the order in which the reference's walk pushes to lFixedCameras.  A key frame that shares
+ *                          nothing with the local points is not listed.
+ * nkf == 0, or local rows without entries: ORBHIP_OK, all counts 0, edge_off_out[0] = 0, nothing launched.  ORBHIP_E_ARG, checked
+ * before any device work, nothing written: no store or table, a key the table does not know, nkf > 65536.  ORBHIP_E_SIZE: more
+ * than 2^24 local row entries.  ORBHIP_E_CAPACITY: any of the three caps is too small; all three counts are written with the true
+ * numbers and no array is.  A failed call changes nothing.  One upload (8 B per local key frame and per table row), one result
+ * block, one synchronisation; scratch only grows.  Integer work: results are exact and two runs give identical bytes.
+ * Precondition for equality with the reference's walk over observation maps: every observer's row is in the table and current,
+ * flags are current. */
+typedef struct orbhip_ba_edge {
+    int32_t kf, idx;
+} orbhip_ba_edge;
+int orbhip_map_ba_problem(orbhip_ctx *ctx, int nkf, const uint64_t *kf_keys, uint64_t *point_keys_out, int cap_points, int *npoints,
+                          int32_t *edge_off_out /* [cap_points + 1] */, orbhip_ba_edge *edges_out, int cap_edges, int *nedges,
+                          uint64_t *fixed_keys_out, int cap_fixed, int *nfixed);
+
 /* ---- SearchByBoW against all candidate key frames in one call ----
  * Tracking::Relocalization (ref: src/Tracking.cc:2595-2616) and LoopClosing::ComputeSim3 (ref: src/LoopClosing.cc:304-332) call
  * ORBmatcher::SearchByBoW once per candidate key frame.  Here one call matches the fixed side against K candidates: every key frame

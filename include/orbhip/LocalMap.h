@@ -274,6 +274,35 @@ public:
     struct CullWays { long device, host; };
     static CullWays &CullWayCounts() { static CullWays w = {0, 0}; return w; }
 
+    // ---- the set-up of local bundle adjustment from the resident key-frame table (orbhip_map_ba_problem; DESIGN.md section 24,
+    // INTEGRATION.md section 3e) ----
+    // What Optimizer::LocalBundleAdjustment forms before the solver sees a vertex (ref: src/Optimizer.cc:2772-2820, :2888 ff.), in one
+    // device call instead of two copies of every local point's observation map:
+    //   vpLocalKFs   the local key frames, as given or as BuildLocalBA forms them
+    //   vpLocalMPs   lLocalMapPoints, in the reference's order
+    //   vpFixedKFs   lFixedCameras: the observers of a local point that are no local key frame, in the order of the reference's walk
+    //                with ascending mnId standing for the order of map<KeyFrame*, size_t> (docs/parity.md)
+    //   vEdgeOff, vEdges   the observations of vpLocalMPs[j] are vEdges[vEdgeOff[j] .. vEdgeOff[j + 1]), ascending mnId: one per
+    //                edge the reference adds.  The caller reads pKF->mvKeysUn[idx] and pKF->mvuRight[idx] itself.
+    // Indices become pointers at the moment of application.  Both calls leave mnBALocalForKF / mnBAFixedForKF on the objects as the
+    // reference does.  Precondition as UpdateConnections': every observer's row is in the table and current, flags are current, a
+    // key frame that turned bad has been erased.  false = a failed device call, or a local key frame without a row: `out` is
+    // empty and the caller runs its own loops (the hiperror.h convention).
+    struct BAEdge { KeyFrame *pKF; size_t idx; };
+    struct BAProblem {
+        std::vector<KeyFrame *> vpLocalKFs, vpFixedKFs;
+        std::vector<MapPoint *> vpLocalMPs;
+        std::vector<int32_t> vEdgeOff;
+        std::vector<BAEdge> vEdges;
+    };
+    // forms the list of :2772-2784 itself: pKF and its GetVectorCovisibleKeyFrames(), every one stamped with pKF->mnId, the bad
+    // ones stamped but not listed
+    bool BuildLocalBA(KeyFrame *pKF, BAProblem &out);
+    // a caller-given window (LocalBundleAdjustmentNavState, :980 ff.; the other LocalBundleAdjustment, :1720 ff.), or every key
+    // frame for BundleAdjustment (:2358 ff.): NULL and bad key frames are left out, the stamp is vpLocalKFs.back()->mnId (the
+    // window's pCurKF).  The key frame before the window, which the windowed forms fix as well, is the caller's to add.
+    bool BuildBAProblem(const std::vector<KeyFrame *> &vpLocalKFs, BAProblem &out);
+
     // ---- map points moved in place on the resident store (orbhip_map_correct_sim3, orbhip_map_correct_se3; DESIGN.md section 23,
     // INTEGRATION.md section 3e) ----
     // A g2o::Sim3 as the call reads it: rotation().coeffs() (x y z w), translation(), scale().  The Sim3 algebra -- the composition
@@ -333,6 +362,7 @@ protected:
     bool FlushLoop(FuseEdits &edits);                             // FlushFuse with one orbhip_map_kf_set_batch (LocalMapLoop.cc)
     bool EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey);
     bool ResidentKeyFrame(KeyFrame *pKF, uint64_t *setKey);       // SearchByBoWCandidates: row and set of a key frame the store knows (LocalMapBowCand.cc)
+    bool BuildBALocked(const std::vector<KeyFrame *> &vpLocalKFs, unsigned long nStamp, BAProblem &out);   // LocalMapBA.cc
 
     orbhip_ctx *mpCtx;
     std::mutex mMutex;
@@ -342,7 +372,8 @@ protected:
     size_t mnLastVoted = 0, mnLastLocal = 0;   // sizes of the last answers: how much room the next call offers first
     size_t mnLastCandidates = 0, mnLastLoopPoints = 0;
     size_t mnLastLinks = 0;                    // links per key frame of the last UpdateConnections, rounded up
-    bool mbFuseSets = false;                   // the set limit has been raised for the targets of FuseInTargets
+    size_t mnLastBAEdges = 0, mnLastBAFixed = 0;   // of the last BuildLocalBA / BuildBAProblem
+    bool mbFuseSets = false;                  // the set limit has been raised for the targets of FuseInTargets
     int mnSetLimit = 4;                        // the set limit in force (orbhip_set_limit)
 };
 

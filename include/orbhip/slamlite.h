@@ -88,6 +88,9 @@ public:
     long unsigned int mnCorrectedReference = 0;
     cv::Mat mPosGBA;                         // 3 x 1 CV_32F
     long unsigned int mnBAGlobalForKF = 0;
+    // Variable used by local mapping (ref: include/MapPoint.h:110): the stamp of Optimizer::LocalBundleAdjustment's point walk,
+    // left by LocalMapSearch::BuildLocalBA / BuildBAProblem
+    long unsigned int mnBALocalForKF = 0;
     static bool &RecomputeOnReplace() { static bool b = false; return b; }
 
     // ref: include/MapPoint.h "long unsigned int mnId; static long unsigned int nNextId;": mnId + 1 is the key under which
@@ -277,6 +280,10 @@ public:
     cv::Mat mTcwGBA;
     cv::Mat mTcwBefGBA;
     long unsigned int mnBAGlobalForKF = 0;
+    // Variables used by the local mapping (ref: include/KeyFrame.h:184-185): the stamps Optimizer::LocalBundleAdjustment leaves on
+    // its local and its fixed key frames (LocalMapSearch::BuildLocalBA / BuildBAProblem)
+    long unsigned int mnBALocalForKF = 0;
+    long unsigned int mnBAFixedForKF = 0;
     cv::Mat Tcw;                                  // 4 x 4 CV_32F (protected in the reference; the test programs fill it)
     cv::Mat Ow;                                   // 3 x 1 CV_32F
 

@@ -588,6 +588,13 @@ void launch_covis(hipStream_t s, const void *rows, int nrows, int stride, int ma
 void launch_cull(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint8_t *levels, const uint32_t *mflags,
                  int maxPoints, uint32_t *marks, const void *cand, int K, uint32_t bound, uint32_t *nids, uint32_t *tally, int monocular,
                  int thObs, void *counts, uint8_t *state);
+// k_baproblem.hip: behind launch_collect(capOut = bound, slots, nlocal = hdr); hdr [3], cnt [bound + 1], cursor [bound] zero and
+// firstPos [nrows] ~0 on entry; rowRank / rowLocal [nrows] = the rank of the row's key / its place among the local key frames, or -1
+void launch_ba_problem(hipStream_t s, const void *rows, int nrows, int stride, int maxRow, const uint32_t *mflags, int maxPoints,
+                       uint32_t *marks, const int32_t *rowRank, const int32_t *rowLocal, int nkf, int32_t *hdr, int bound,
+                       const int32_t *slots, uint32_t *cnt, uint32_t *off, uint32_t *cursor, void *raw, void *sorted, uint32_t capRaw,
+                       uint32_t *firstPos, void *list, int32_t *fixedRank, int capP, int capE, int capF, int32_t *resHdr,
+                       int32_t *resSlots, int32_t *resOff, int32_t *resFixed, void *resEdges);
 // desc [m] = {table row, first byte, length}: the level bytes of m key frames into levels [maxKfs][maxRow]
 void launch_cull_levels(hipStream_t s, const uint8_t *bytes, const int32_t *desc, int m, int maxKfs, int maxRow, uint8_t *levels);
 void launch_collect(hipStream_t s, const void *rows, int nrows, int stride, const int32_t *rowIdx, const uint32_t *off, int nkf,

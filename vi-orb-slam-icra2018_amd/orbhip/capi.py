@@ -75,6 +75,7 @@ SYMBOLS = [
     "orbhip_map_refresh", "orbhip_map_get", "orbhip_map_covis", "orbhip_search_by_bow_candidates",
     "orbhip_map_kf_levels", "orbhip_map_kf_levels_missing", "orbhip_map_cull",
     "orbhip_map_correct_sim3", "orbhip_map_correct_se3",
+    "orbhip_map_ba_problem",
 ]
 
 
@@ -262,6 +263,7 @@ def load():
     L.orbhip_map_kf_levels.argtypes = [vp, i32, vp, vp, vp]
     L.orbhip_map_kf_levels_missing.argtypes = [vp, vp, i32, ip]
     L.orbhip_map_cull.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp]
+    L.orbhip_map_ba_problem.argtypes = [vp, i32, vp, vp, i32, ip, vp, vp, i32, ip, vp, i32, ip]
     L.orbhip_map_correct_sim3.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_correct_se3.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.orbhip_search_by_bow_candidates.argtypes = [vp, i32, u64, u64, vp, i32, i32, f32, i32, vp, vp, i32, vp, i32, f32, vp, vp, vp,

@@ -246,6 +246,24 @@ class LocalMap:
         out = (counts[:K].copy(), red[:K].astype(bool))
         return out + (st[:K].copy(),) if want_entries else out
 
+    # ---- the structure of local bundle adjustment's problem ----
+    def ba_problem(self, kf_keys, cap_points, cap_edges, cap_fixed):
+        """orbhip_map_ba_problem for the local key frames kf_keys: (point_keys, edge_off [npoints + 1], edges [nedges][2] = kf, idx,
+        fixed_keys).  kf < len(kf_keys) names kf_keys[kf], otherwise fixed_keys[kf - len(kf_keys)].  The buffers start as 7 / -7 so
+        that a caller sees what a failed call left alone (e.outputs); e.counts has the three counts as the call left them."""
+        kk = np.ascontiguousarray(kf_keys, np.uint64)
+        pts, fixed = np.full(max(cap_points, 1), 7, np.uint64), np.full(max(cap_fixed, 1), 7, np.uint64)
+        off, edges = np.full(max(cap_points, 0) + 1, -7, np.int32), np.full((max(cap_edges, 1), 2), -7, np.int32)
+        n_p, n_e, n_f = C.c_int(-7), C.c_int(-7), C.c_int(-7)
+        try:
+            check(self._L.orbhip_map_ba_problem(self._ctx.handle, len(kk), _p(kk), _p(pts), cap_points, C.byref(n_p), _p(off), _p(edges),
+                                                cap_edges, C.byref(n_e), _p(fixed), cap_fixed, C.byref(n_f)), self._ctx.handle,
+                  "orbhip_map_ba_problem")
+        except capi.OrbHipError as e:
+            e.outputs, e.counts = (pts, off, edges, fixed), (n_p.value, n_e.value, n_f.value)
+            raise
+        return pts[:n_p.value].copy(), off[:n_p.value + 1].copy(), edges[:n_e.value].copy(), fixed[:n_f.value].copy()
+
     def search_by_bow_candidates(self, mode, fixed_set_key, fixed_row_key, n_fixed, candidates, th=50, nnratio=0.75, check_ori=True,
                                  gather=None, cap=None):
         """orbhip_search_by_bow_candidates: SearchByBoW of the fixed set of n_fixed features against K

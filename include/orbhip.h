@@ -942,6 +942,46 @@ int orbhip_search_loop_points(orbhip_ctx *ctx, const orbhip_fuse_target *target,
                               orbhip_proj_query *queries_out, int *n_active, int32_t *match, int *nmatches);
 int orbhip_map_kf_set_batch(orbhip_ctx *ctx, int m, const uint64_t *kf_keys, const int32_t *idx, const uint64_t *point_keys);
 
+/* ---- ORBmatcher::SearchBySim3 on the resident map ----
+ * LoopClosing::ComputeSim3 calls SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, 7.5) (ref: src/ORBmatcher.cc:1102-1326,
+ * src/LoopClosing.cc:375) after every successful solver iteration: the points of each key frame are carried into the other camera,
+ * searched there, and a pair counts when the two directions name each other.  Everything it reads is resident: the points in the
+ * store, mvpMapPoints of both key frames in the key-frame table, both feature sets with their grids.  One pair of key frames per call.
+ *   sides [2]       side 1, side 2: set_key = the key frame's resident set, put with a grid; cam = its Rcw / tcw (world -> camera),
+ *                   intrinsics, image bounds, scale_factors, log_scale_factor, nlevels.  Ow, mbf, viewing_cos_limit, th and
+ *                   inv_level_sigma2 are not read; level_ratio is filled by the call.
+ *   row_keys [2]    the sides' rows in the key-frame table; each row must be as long as its set has features (the matches index both)
+ *   sR21, t21       [9] row-major, [3]: carry a point of camera 1 into camera 2 (the reference's (1.0/s12)*R12.t() and -sR21*t12);
+ *   sR12, t12       the other way (s12*R12, t12).  The caller composes them on the host, as it decomposes Scw for orbhip_fuse_sim3.
+ *   th, th_high     the window factor (ComputeSim3 passes 7.5) and the bound on the best distance (TH_HIGH = 100)
+ *   taken1 [n1], taken2 [n2] or NULL: vbAlreadyMatched1 / vbAlreadyMatched2 (:1129-1142), non-zero = the entry stays out
+ *   match12 [n1]    the feature of key frame 2 of every agreed pair (:1310-1323), -1 elsewhere; *nfound = their number
+ *   n_active [2]    the ORBHIP_Q_ACTIVE queries of direction 0 (row 1 into set 2) and direction 1 (row 2 into set 1)
+ *   queries1_out, best1, dist1 [n1]; queries2_out, best2, dist2 [n2], each may be NULL: the queries as the kernel wrote them (an
+ *                   inactive one is all zero; proj_xr is 0) and what the loops of :1196-1219 / :1276-1299 find, as
+ *                   orbhip_window_best_set defines them with inv_level_sigma2 == NULL (no chi-square gate; -1 / 256: inactive, or
+ *                   no feature closer than 256).  match12[i1] = best1[i1] if dist1[i1] <= th_high and, with i2 = best1[i1],
+ *                   dist2[i2] <= th_high and best2[i2] == i1.
+ * An entry is active when it resolves (live, not ORBHIP_MP_BAD, the entry's generation), its taken byte is 0, z >= 0 (`< 0.0`
+ * skips), the projection lies inside the DESTINATION's half-open IsInImage bounds and 0.8f * mfMinDistance <= dist3D <=
+ * 1.2f * mfMaxDistance.  The arithmetic is the reference's: p = Rsw * Xw + tsw rounded to float, then sR * p + t, one gemm each
+ * (double sums, one rounding); invz = 1 / z in float; x = X * invz and then u = fx * x + cx, each operation rounded (Fuse's
+ * association); dist3D = cv::norm of the CAMERA point (there is no P - Ow here); no viewing-angle test; PredictScale(dist3D,
+ * destination), radius = th * scale_factors[level], levels [level - 1, level], the first feature of smallest distance.
+ * One quirk of the reference is kept: fx, fy, cx, cy are SIDE 1's in both directions (:1105-1108, used at :1170 and :1250); bounds,
+ * scale tables and grid are the destination's.  sides[1].cam's intrinsics are therefore not read.
+ * row_keys[0] == row_keys[1] (with the same set) is legal.  Two rows without a point: counts 0, match12 all -1, nothing is launched.
+ * One upload (two camera records, the similarity, the taken bytes), one result block, one synchronisation.
+ * ORBHIP_E_ARG, with no output touched: no store or table, an unknown row or set, a set without a grid, a row whose length is not
+ * its set's feature count, nlevels outside 1..16, a th that is not finite, more distinct sets than the set limit in force.
+ * ORBHIP_E_SIZE, likewise: a set of 2^20 features or more.
+ * Divergences from the reference, by design: as orbhip_fuse_row (dist3D == 0 or not finite, a non-finite mfMaxDistance / dist3D,
+ * an entry that does not resolve: inactive). */
+int orbhip_search_by_sim3(orbhip_ctx *ctx, const orbhip_fuse_target *sides, const uint64_t *row_keys, const float *sR21,
+                          const float *t21, const float *sR12, const float *t12, float th, int th_high, const uint8_t *taken1,
+                          const uint8_t *taken2, int32_t *match12, int *nfound, int32_t *n_active, orbhip_proj_query *queries1_out,
+                          int32_t *best1, int32_t *dist1, orbhip_proj_query *queries2_out, int32_t *best2, int32_t *dist2);
+
 /* ---- map points refreshed in place on the resident store ----
  * MapPoint::ComputeDistinctiveDescriptors (ref: src/MapPoint.cc:257-322) and MapPoint::UpdateNormalAndDepth (ref: :345-386) for a
  * batch of points, from their observation lists: the observers' descriptors and octaves are read from the resident feature sets, the

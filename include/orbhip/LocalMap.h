@@ -167,6 +167,16 @@ public:
     // for the tests: without the second search of changed survivors the result differs from the reference's
     static bool &ResearchChangedSurvivors() { static bool b = true; return b; }
 
+    // ---- ORBmatcher::SearchBySim3 on the resident map (orbhip_search_by_sim3) ----
+    // matcher.SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) of LoopClosing::ComputeSim3 (ref: src/ORBmatcher.cc:1102-1326,
+    // src/LoopClosing.cc:375): the same return value and the same edits to vpMatches12.  Both key frames' points are those of
+    // their rows in the table, both feature sets become resident the first time; the two projections, the two window searches
+    // and the agreement are one device call, and vpMatches12[i1] = pKF2->GetMapPointMatches()[i2] for the agreed pairs.  Returns
+    // -1 with vpMatches12 untouched -- the caller then runs ORBmatcher::SearchBySim3 -- when a key frame has no row (PutKeyFrame),
+    // when a key frame holds a non-NULL, non-bad point that was never Put, or when the device call fails (hiperror.h).
+    int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12, const float &s12, const cv::Mat &R12,
+                     const cv::Mat &t12, const float th);
+
     // ---- map points refreshed in place on the resident store (orbhip_map_refresh) ----
     // The loops "pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth();" over a key frame's points (ref:
     // src/LocalMapping.cc:2036-2046, :2577-2590; the UpdateNormalAndDepth loops of src/Optimizer.cc with bDescriptors = false) as one

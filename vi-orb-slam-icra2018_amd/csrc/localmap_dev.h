@@ -1,5 +1,5 @@
 // localmap_dev.h -- device helpers shared by the kernels that read the resident map-point store (k_localmap.hip,
-// k_localcollect.hip, k_covis.hip, k_cull.hip, k_baproblem.hip, k_projtrack.hip, k_fuse.hip, k_loopfuse.hip, k_bowcand.hip and k_hamming.hip through bow_match_dev.h) and by the window searches (k_guided.hip, k_fuse.hip): the
+// k_localcollect.hip, k_covis.hip, k_cull.hip, k_baproblem.hip, k_projtrack.hip, k_fuse.hip, k_loopfuse.hip, k_sim3search.hip, k_bowcand.hip and k_hamming.hip through bow_match_dev.h) and by the window searches (k_guided.hip, k_fuse.hip): the
 // flag-word rules, the reference's gemm, the key-frame row entry, the per-batch count of active queries, the cell window of
 // GetFeaturesInArea and the 16-lane window walk that k_window_best_row and k_window_best_sets share.
 #ifndef ORBHIP_LOCALMAP_DEV_H

@@ -1,5 +1,5 @@
 // localmap_store.h -- the host side of the resident map-point store and of the key-frame table, shared by the api_*.hip files
-// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip, api_cull.hip, api_baproblem.hip): device blocks, the key -> slot / key -> row
+// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip, api_sim3search.hip, api_cull.hip, api_baproblem.hip): device blocks, the key -> slot / key -> row
 // tables, what a call over several rows of the table (the ordered union) sets up, and the target records of the Fuse calls.
 #ifndef ORBHIP_LOCALMAP_STORE_H
 #define ORBHIP_LOCALMAP_STORE_H

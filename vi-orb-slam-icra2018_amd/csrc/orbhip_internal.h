@@ -574,6 +574,15 @@ void launch_project_fuse_sim3(hipStream_t s, const void *geoA, const void *geoB,
 // k_loopfuse.hip
 void launch_loop_held(hipStream_t s, const void *rows, int stride, int maxRow, const int32_t *rowIdx, int K, int maxLen,
                       const uint32_t *mflags, int maxPoints, uint32_t *marks, const int32_t *slots, int n, uint8_t *skip);
+// k_sim3search.hip
+size_t sim3_pair_bytes();   // the pair record of the search, written by sim3_pair_fill
+void sim3_pair_fill(void *dst, const float *sR21, const float *t21, const float *sR12, const float *t12, int row1, int row2, int n1,
+                    int n2, float th, int thHigh);
+void launch_project_sim3(hipStream_t s, const void *geoA, const void *geoB, const uint32_t *mflags, int maxPoints, const void *rows,
+                         int stride, int maxRow, const void *pair, const orbhip_local_camera *cams, const uint8_t *taken1,
+                         const uint8_t *taken2, int capQ, orbhip_proj_query *queries, int32_t *slotsOut, int32_t *nActive);
+void launch_sim3_agree(hipStream_t s, const void *pair, const int32_t *bestIdx, const int32_t *bestDist, int capQ, int n1,
+                       int32_t *match12, int32_t *nfound);
 // k_localcollect.hip
 void launch_mark_add(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);
 void launch_mark_clear(hipStream_t s, const int32_t *slots, int n, int maxPoints, uint32_t *marks);

@@ -1,4 +1,4 @@
-// LocalMapDetail.h -- what LocalMap.cc, LocalMapCollect.cc, LocalMapProjTrack.cc, LocalMapFuse.cc, LocalMapLoop.cc, LocalMapRefresh.cc, LocalMapCovis.cc, LocalMapCull.cc, LocalMapBA.cc, LocalMapCorrect.cc and LocalMapBowCand.cc share: keys and flags of a MapPoint, the frame as a resident
+// LocalMapDetail.h -- what LocalMap.cc, LocalMapCollect.cc, LocalMapProjTrack.cc, LocalMapFuse.cc, LocalMapLoop.cc, LocalMapSim3.cc, LocalMapRefresh.cc, LocalMapCovis.cc, LocalMapCull.cc, LocalMapBA.cc, LocalMapCorrect.cc and LocalMapBowCand.cc share: keys and flags of a MapPoint, the frame as a resident
 // set, the camera block of a search and the write-back of its results (ref: src/Tracking.cc:2336-2364, src/Frame.cc:613-669,
 // src/ORBmatcher.cc:45-129).
 #ifndef ORBHIP_LOCALMAP_DETAIL_H

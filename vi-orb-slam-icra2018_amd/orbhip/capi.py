@@ -71,7 +71,7 @@ SYMBOLS = [
     "orbhip_pnp_score", "orbhip_pnp_score_device", "orbhip_sim3_score", "orbhip_sim3_score_device",
     "orbhip_search_for_triangulation_sets",
     "orbhip_fuse_row", "orbhip_fuse_collect",
-    "orbhip_fuse_sim3", "orbhip_search_loop_points", "orbhip_map_kf_set_batch",
+    "orbhip_fuse_sim3", "orbhip_search_loop_points", "orbhip_map_kf_set_batch", "orbhip_search_by_sim3",
     "orbhip_map_refresh", "orbhip_map_get", "orbhip_map_covis", "orbhip_search_by_bow_candidates",
     "orbhip_map_kf_levels", "orbhip_map_kf_levels_missing", "orbhip_map_cull",
     "orbhip_map_correct_sim3", "orbhip_map_correct_se3",
@@ -257,6 +257,7 @@ def load():
     L.orbhip_fuse_sim3.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp, vp, vp]
     L.orbhip_search_loop_points.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, ip, vp, ip, vp, ip]
     L.orbhip_map_kf_set_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.orbhip_search_by_sim3.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_float, i32, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_refresh.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_get.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_map_covis.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, i32, ip]

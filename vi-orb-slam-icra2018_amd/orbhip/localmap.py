@@ -436,6 +436,32 @@ class LocalMap:
         m = npts.value
         return keys[:m].copy(), (None if q is None else q[:m].copy()), na.value, nm.value, match[:n].copy()
 
+    # ---- ORBmatcher::SearchBySim3 on the resident map ----
+    def search_by_sim3(self, sides, row_keys, n1, n2, sR21, t21, sR12, t12, th, th_high=100, taken1=None, taken2=None, want=True):
+        """orbhip_search_by_sim3.  sides: two fuse_target records (side 1, side 2; cam = the key frame's own pose), row_keys [2],
+        n1 / n2 = the lengths of the two rows (= the sets' feature counts), the similarity composed by the caller, taken1 [n1] /
+        taken2 [n2] bytes or None.  Returns (match12 [n1], nfound, n_active [2], (queries1, best1, dist1), (queries2, best2,
+        dist2)); with want=False the optional outputs are passed as NULL and the two tuples come back None."""
+        t = np.ascontiguousarray(sides, FUSE_TARGET_DTYPE).ravel()
+        rk = np.ascontiguousarray(row_keys, np.uint64).ravel()
+        assert len(t) == 2 and len(rk) == 2
+        sim = [np.ascontiguousarray(a, f32).ravel() for a in (sR21, t21, sR12, t12)]
+        assert [len(a) for a in sim] == [9, 3, 9, 3]
+        tk1 = None if taken1 is None else np.ascontiguousarray(taken1, np.uint8).ravel()
+        tk2 = None if taken2 is None else np.ascontiguousarray(taken2, np.uint8).ravel()
+        assert (tk1 is None or len(tk1) == n1) and (tk2 is None or len(tk2) == n2)
+        match = np.empty(max(n1, 1), np.int32)
+        nf, na = C.c_int(), np.zeros(2, np.int32)
+        opt = [None] * 6
+        if want:
+            opt = [a for n in (n1, n2) for a in (np.zeros(max(n, 1), QUERY_DTYPE), np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32))]
+        check(self._L.orbhip_search_by_sim3(self._ctx.handle, _p(t), _p(rk), _p(sim[0]), _p(sim[1]), _p(sim[2]), _p(sim[3]), C.c_float(th),
+                                            th_high, _p(tk1), _p(tk2), _p(match), C.byref(nf), _p(na), *[_p(a) for a in opt]),
+              self._ctx.handle, "orbhip_search_by_sim3")
+        if not want:
+            return match[:n1].copy(), nf.value, na.copy(), None, None
+        return (match[:n1].copy(), nf.value, na.copy(), tuple(a[:n1].copy() for a in opt[:3]), tuple(a[:n2].copy() for a in opt[3:]))
+
     # ---- map points refreshed in place: descriptor, normal, depth (DESIGN.md section 19) ----
     def map_refresh(self, scale_factors, nlevels, what, kfs, point_keys, off, obs_kf, obs_idx, ref_pos, want=True):
         """orbhip_map_refresh.  kfs: REFRESH_KF_DTYPE records; the lists as CSR (off [P + 1], obs_kf / obs_idx [off[P]]) in ascending

@@ -27,10 +27,7 @@ extern "C" int orbhip_fuse_row(orbhip_ctx *c, uint64_t src_row_key, const orbhip
     if (K > FUSE_MAX_TARGETS || (int64_t)K * n > FUSE_MAX_QUERIES)
         return fail(c, ORBHIP_E_SIZE, std::string(who) + ": more than 65535 targets, or K * n beyond 2^24");
     std::vector<orbhip_local_camera> cams(K);
-    for (int k = 0; k < K; k++) {
-        cams[k] = targets[k].cam;
-        if ((rc = orbhip_local_camera_prepare(c, &cams[k]))) return rc;
-    }
+    if ((rc = fuse_cameras_prepare(c, targets, K, cams.data()))) return rc;
     const size_t total = (size_t)K * n;
     for (int k = 0; k < K; k++) n_active[k] = 0;
     for (size_t i = 0; i < total; i++) best_idx[i] = -1, best_dist[i] = 256;
@@ -50,15 +47,7 @@ extern "C" int orbhip_fuse_row(orbhip_ctx *c, uint64_t src_row_key, const orbhip
     const orbhip_local_camera *dcam = (const orbhip_local_camera *)P.in(cams.data(), (size_t)K * sizeof(orbhip_local_camera));
     const uint8_t *dskip = skip ? (const uint8_t *)P.in(skip, total) : nullptr;
     const float *dur = u_right ? (const float *)P.in(u_right, T.urTotal * 4) : nullptr;
-    uint8_t *htab;
-    const void *dtab = P.in_reserve((size_t)K * tb, (void **)&htab);
-    size_t urAt = 0;
-    for (int k = 0; k < K; k++) {
-        const OrbSetView &S = T.view[k];
-        fuse_target_fill(htab + (size_t)k * tb, S.d_kps, S.d_desc, S.d_cellOff, S.d_cellIdx, scratch + T.recOff[k], dur ? dur + urAt : nullptr,
-                         S.minX, S.minY, S.invW, S.invH, S.n, targets[k].inv_level_sigma2);
-        urAt += (size_t)S.n;
-    }
+    const void *dtab = fuse_targets_pack(P, T, scratch, targets, dur);
     int32_t *dna = (int32_t *)P.in_fill(0, (size_t)K * 4);   // the active counts (come back with what follows)
     int32_t *dbi = (int32_t *)P.out(total * 4), *dbd = (int32_t *)P.out(total * 4);
     orbhip_proj_query *dq = queries_out ? (orbhip_proj_query *)P.out(qBytes) : (orbhip_proj_query *)(scratch + T.recBytes + slotBytes);
@@ -132,10 +121,7 @@ extern "C" int orbhip_fuse_collect(orbhip_ctx *c, const orbhip_fuse_target *targ
         hown[i] = (s >= 0 && s < M->maxPoints && M->slotKey[s] != 0 && M->gen[s] == (uint32_t)(own[i] >> 32)) ? s : -1;
     }
     const float *dur = u_right ? (const float *)P.in(u_right, (size_t)S.n * 4) : nullptr;
-    uint8_t *htab;
-    const void *dtab = P.in_reserve(tb, (void **)&htab);
-    fuse_target_fill(htab, S.d_kps, S.d_desc, S.d_cellOff, S.d_cellIdx, scratch, dur, S.minX, S.minY, S.invW, S.invH, S.n,
-                     target->inv_level_sigma2);
+    const void *dtab = fuse_targets_pack(P, T, scratch, target, dur);
     const int32_t cnts[4] = {0, 0, 0, 0};
     int32_t *dc = (int32_t *)P.in(cnts, 16);   // candidates | active queries (come back with what follows)
     int32_t *dslots = (int32_t *)P.out((size_t)capQ * 4);
@@ -153,11 +139,11 @@ extern "C" int orbhip_fuse_collect(orbhip_ctx *c, const orbhip_fuse_target *targ
     HIPCHK(c, hipGetLastError());
     if ((rc = P.download(dc))) return rc;   // counts | slots | best_idx | best_dist | queries: one copy back, one synchronisation
     const int32_t *hc = (const int32_t *)P.host(dc);
-    const int32_t *hs = (const int32_t *)P.host(dslots);
     const int got = hc[0];
     *ncand = got;
-    for (int i = 0; i < std::min(got, capQ); i++) keys_out[i] = (hs[i] >= 0 && hs[i] < M->maxPoints) ? M->slotKey[hs[i]] : 0;
-    if (got > cap) return fail(c, ORBHIP_E_CAPACITY, std::string(who) + ": more candidates than cap (*ncand has the number)");
+    if ((rc = collect_keys_out(c, M, (const int32_t *)P.host(dslots), got, capQ, cap, keys_out,
+                               std::string(who) + ": more candidates than cap (*ncand has the number)")))
+        return rc;
     *n_active = hc[1];
     memcpy(best_idx, P.host(dbi), (size_t)got * 4);
     memcpy(best_dist, P.host(dbd), (size_t)got * 4);

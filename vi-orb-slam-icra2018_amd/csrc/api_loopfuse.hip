@@ -43,10 +43,7 @@ extern "C" int orbhip_fuse_sim3(orbhip_ctx *c, const orbhip_fuse_target *targets
         if (std::adjacent_find(k.begin(), k.end()) != k.end()) return fail(c, ORBHIP_E_ARG, std::string(who) + ": a key twice in point_keys");
     }
     std::vector<orbhip_local_camera> cams(K);
-    for (int k = 0; k < K; k++) {
-        cams[k] = targets[k].cam;
-        if ((rc = orbhip_local_camera_prepare(c, &cams[k]))) return rc;
-    }
+    if ((rc = fuse_cameras_prepare(c, targets, K, cams.data()))) return rc;
     for (int k = 0; k < K; k++) n_active[k] = 0;
     if (n == 0) return ORBHIP_OK;
     const size_t total = (size_t)K * n;
@@ -68,13 +65,7 @@ extern "C" int orbhip_fuse_sim3(orbhip_ctx *c, const orbhip_fuse_target *targets
     kf_mark_slots(M, point_keys, n, hslots);   // -1 for key 0 and for keys the store does not know
     const int32_t cnts[4] = {n, 0, 0, 0};
     const int32_t *dn = (const int32_t *)P.in(cnts, 16);
-    uint8_t *htab;
-    const void *dtab = P.in_reserve((size_t)K * tb, (void **)&htab);
-    for (int k = 0; k < K; k++) {
-        const OrbSetView &S = T.view[k];
-        fuse_target_fill(htab + (size_t)k * tb, S.d_kps, S.d_desc, S.d_cellOff, S.d_cellIdx, scratch + T.recOff[k], nullptr, S.minX, S.minY,
-                         S.invW, S.invH, S.n, targets[k].inv_level_sigma2);
-    }
+    const void *dtab = fuse_targets_pack(P, T, scratch, targets, nullptr);
     int32_t *dna = (int32_t *)P.in_fill(0, (size_t)K * 4);   // the active counts (come back with what follows)
     int32_t *dbi = (int32_t *)P.out(total * 4), *dbd = (int32_t *)P.out(total * 4);
     orbhip_proj_query *dq = queries_out ? (orbhip_proj_query *)P.out(qBytes) : (orbhip_proj_query *)(scratch + T.recBytes + slotBytes + skipBytes);
@@ -178,11 +169,11 @@ extern "C" int orbhip_search_loop_points(orbhip_ctx *c, const orbhip_fuse_target
     }
     if ((rc = P.download(dc))) return rc;   // counts | slots | matches | queries: one copy back, one synchronisation
     const int32_t *hc = (const int32_t *)P.host(dc);
-    const int32_t *hs = (const int32_t *)P.host(dslots);
     const int got = hc[0];
     *npoints = got;
-    for (int i = 0; i < std::min(got, capQ); i++) keys_out[i] = (hs[i] >= 0 && hs[i] < M->maxPoints) ? M->slotKey[hs[i]] : 0;
-    if (got > cap) return fail(c, ORBHIP_E_CAPACITY, std::string(who) + ": more points than cap (*npoints has the number)");
+    if ((rc = collect_keys_out(c, M, (const int32_t *)P.host(dslots), got, capQ, cap, keys_out,
+                               std::string(who) + ": more points than cap (*npoints has the number)")))
+        return rc;
     *n_active = hc[1];
     if (search) {
         memcpy(match, P.host(dm), (size_t)n * 4);

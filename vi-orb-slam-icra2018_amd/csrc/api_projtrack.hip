@@ -3,10 +3,7 @@
 // (Relocalization, ref: :1500-1627).  The projection kernels (k_projtrack.hip) write the queries, the window search of
 // k_guided.hip reads the points' descriptors from the store by slot.  As orbhip_search_local_points: one packed upload, one
 // dependency chain, one result block, one synchronisation.
-#include "localmap_store.h"
-
-// the per-level table of a camera record as both searches need it
-static bool camera_ok(const orbhip_local_camera *cam) { return cam->nlevels >= 1 && cam->nlevels <= 16 && std::isfinite(cam->th); }
+#include "localmap_store.h"   // fuse_camera_ok: the per-level table of a camera record as both searches need it
 
 // projection -> queries (the caller's block, or the matching scratch behind what the window search carves from it) -> window
 // search.  d_n_active must be zero (zeroIt: a memset node in front).
@@ -74,7 +71,7 @@ extern "C" int orbhip_search_last_frame(orbhip_ctx *c, uint64_t cur_key, uint64_
         return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: last_key is an unknown set");
     if (n_last != L.n) return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: n_last differs from the size of the last frame's set");
     if (motion < 0 || motion > 2) return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: motion outside 0..2");
-    if (!camera_ok(cam)) return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: nlevels outside 1..16, or th not finite");
+    if (!fuse_camera_ok(cam)) return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: nlevels outside 1..16, or th not finite");
     if (n_last > 0 && (L.octMin < 0 || L.octMax >= cam->nlevels))
         return fail(c, ORBHIP_E_ARG, "orbhip_search_last_frame: the last frame's set has an octave outside [0, nlevels)");
     if (S.n >= (1 << 19) || proj_assign_lds(S.n) > 120 * 1024)
@@ -133,7 +130,7 @@ extern "C" int orbhip_search_keyframe_points(orbhip_ctx *c, uint64_t cur_key, ui
     if (it == K->rowOf.end()) return fail(c, ORBHIP_E_ARG, "orbhip_search_keyframe_points: unknown key frame (orbhip_map_kf_put)");
     const int row = it->second, nq = (int)K->entries[row].size();
     if (nq != F.n) return fail(c, ORBHIP_E_ARG, "orbhip_search_keyframe_points: the key frame's row and its set differ in length");
-    if (!camera_ok(cam)) return fail(c, ORBHIP_E_ARG, "orbhip_search_keyframe_points: nlevels outside 1..16, or th not finite");
+    if (!fuse_camera_ok(cam)) return fail(c, ORBHIP_E_ARG, "orbhip_search_keyframe_points: nlevels outside 1..16, or th not finite");
     if (S.n >= (1 << 19) || proj_assign_lds(S.n) > 120 * 1024)
         return fail(c, ORBHIP_E_SIZE, "orbhip_search_keyframe_points: the frame has too many features for the match table in LDS");
     orbhip_local_camera cm = *cam;

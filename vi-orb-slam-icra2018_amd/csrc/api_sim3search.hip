@@ -38,11 +38,9 @@ extern "C" int orbhip_search_by_sim3(orbhip_ctx *c, const orbhip_fuse_target *si
         return fail(c, ORBHIP_E_ARG, std::string(who) + ": a row is not as long as its set has features (the matches index both)");
     const int capQ = std::max(n1, n2);
     if ((int64_t)2 * capQ > FUSE_MAX_QUERIES) return fail(c, ORBHIP_E_SIZE, std::string(who) + ": 2 * n beyond 2^24");
-    orbhip_local_camera cams[2] = {sides[0].cam, sides[1].cam};
-    for (int s = 0; s < 2; s++) {
-        cams[s].th = th;
-        if ((rc = orbhip_local_camera_prepare(c, &cams[s]))) return rc;
-    }
+    orbhip_local_camera cams[2];
+    if ((rc = fuse_cameras_prepare(c, sides, 2, cams))) return rc;
+    cams[0].th = cams[1].th = th;
     // every check has passed: the outputs as two rows without a point leave them
     *nfound = 0;
     n_active[0] = n_active[1] = 0;
@@ -87,13 +85,7 @@ extern "C" int orbhip_search_by_sim3(orbhip_ctx *c, const orbhip_fuse_target *si
     sim3_pair_fill(hpair, sR21, t21, sR12, t12, row[0], row[1], n1, n2, th, th_high);
     const uint8_t *dtk1 = taken1 ? (const uint8_t *)P.in(taken1, (size_t)n1) : nullptr;
     const uint8_t *dtk2 = taken2 ? (const uint8_t *)P.in(taken2, (size_t)n2) : nullptr;
-    uint8_t *htab;
-    const void *dtab = P.in_reserve(2 * tb, (void **)&htab);
-    for (int k = 0; k < 2; k++) {
-        const OrbSetView &S = T.view[k];
-        fuse_target_fill(htab + (size_t)k * tb, S.d_kps, S.d_desc, S.d_cellOff, S.d_cellIdx, scratch + T.recOff[k], nullptr, S.minX, S.minY,
-                         S.invW, S.invH, S.n, dst[k].inv_level_sigma2);
-    }
+    const void *dtab = fuse_targets_pack(P, T, scratch, dst, nullptr);
     int32_t *dc = (int32_t *)P.in_fill(0, 16);   // active queries of the two directions | matches (come back with what follows)
     int32_t *dm = (int32_t *)P.out((size_t)n1 * 4);
     int32_t *dbi = wantB ? (int32_t *)P.out(total * 4) : (int32_t *)spare;

@@ -1,6 +1,7 @@
-// bow_rot_dev.h -- the rotation-consistency check of SearchByBoW on the device (ref: src/ORBmatcher.cc:236-246, :267-285,
-// ComputeThreeMaxima :1629-1670): the bin of a match and the three bins that survive.  One copy for k_bow_seq, k_bow_lane
-// (k_bowseq.hip) and k_bow_rot_cands (k_bowcand.hip).  Device code only.
+// bow_rot_dev.h -- the rotation-consistency check of the matchers on the device (SearchByBoW, ref: src/ORBmatcher.cc:236-246,
+// :267-285; SearchByProjection, :1458-1494; SearchForInitialization, :473-507; ComputeThreeMaxima :1629-1670): the bin of a match
+// and the three bins that survive.  One copy for k_bow_seq, k_bow_lane (k_bowseq.hip), k_bow_rot_cands (k_bowcand.hip) and
+// k_proj_assign, k_proj_assign_par, k_init_assign (k_guided.hip).  The name is the first user's.  Device code only.
 #ifndef ORBHIP_BOW_ROT_DEV_H
 #define ORBHIP_BOW_ROT_DEV_H
 #include <hip/hip_runtime.h>

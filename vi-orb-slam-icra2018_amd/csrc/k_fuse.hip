@@ -12,15 +12,11 @@
 //                        per-target record selected by blockIdx.y, the chi-square gate on (Fuse) or off (Fuse with a similarity,
 //                        DESIGN.md section 18) and the query's descriptor read from the store by slot.
 // The arithmetic of k_project_fuse is that of Fuse, operation for operation, not that of the frame searches (k_projtrack.hip):
-// the camera point is one gemm (double sums, one rounding); invz = 1 / z is a FLOAT division (the host path's kf_window divides in
-// double and rounds: the two agree for every float, docs/parity.md); x = xc * invz and then u = fx * x + cx, each operation rounded
-// on its own -- the frame searches associate (fx * xc) * invz; the bounds are KeyFrame::IsInImage's, with the maximum OUTSIDE and
-// NaN failing; dist3D is cv::norm (double sum of squares, square root, one rounding); the viewing test compares Mat::dot (double,
-// from 0.0) with 0.5 * (double)dist3D.
+// `zc < 0` rejects, the pinhole is fuse_pinhole (project_dev.h, as are the other shared steps), dist3D is cv::norm of P - Ow, and
+// the viewing test compares Mat::dot, unrounded, with 0.5 * (double)dist3D.
 // Divergences from the reference, by design (it reaches undefined behaviour there): dist3D == 0 or not
-// finite, a non-finite mfMaxDistance / dist3D, and an entry that does not resolve are inactive.  z == 0 and non-finite positions
-// need no rule of their own: u or v is then infinite or NaN and fails IsInImage, as in the reference.
-#include "localmap_dev.h"
+// finite, a non-finite mfMaxDistance / dist3D, and an entry that does not resolve are inactive.
+#include "project_dev.h"
 
 #include <cstring>
 
@@ -52,7 +48,7 @@ __global__ __launch_bounds__(256) void k_project_fuse(const float4 *__restrict__
     if (iq < capQ) {
         const orbhip_local_camera &C = cams[b];
         const size_t at = (size_t)b * capQ + iq;
-        orbhip_proj_query q = {0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0};
+        orbhip_proj_query q = empty_query();
         int s = -1;
         if (iq < NQ) {                                                     // !pMP, isBad() (ref: :844-848)
             if (ROW) {
@@ -67,37 +63,21 @@ __global__ __launch_bounds__(256) void k_project_fuse(const float4 *__restrict__
         if (take && marks) take = marks[s] == 0u;                          // IsInKeyFrame(pKF): the target's own row, marked
         if (take) {
             const float4 A = geoA[s], N = geoB[s];                         // {P, mfMinDistance}, {normal, mfMaxDistance}
+            ProjPixel px;
             do {
-                const float xc = gemm_row(C.Rcw, C.tcw[0], A.x, A.y, A.z); // :850-851
-                const float yc = gemm_row(C.Rcw + 3, C.tcw[1], A.x, A.y, A.z);
-                const float zc = gemm_row(C.Rcw + 6, C.tcw[2], A.x, A.y, A.z);
-                if (zc < 0.0f) break;                                      // :854
-                const float invz = __fdiv_rn(1.0f, zc);                    // :857 (a float division)
-                const float x = __fmul_rn(xc, invz), y = __fmul_rn(yc, invz);
-                const float u = __fadd_rn(__fmul_rn(C.fx, x), C.cx);       // :861-862
-                const float v = __fadd_rn(__fmul_rn(C.fy, y), C.cy);
-                if (!(u >= C.min_x && u < C.max_x && v >= C.min_y && v < C.max_y)) break;   // :865, src/KeyFrame.cc IsInImage
-                const float ur = SIM3 ? 0.0f : __fsub_rn(u, __fmul_rn(C.mbf, invz));   // :868; Fuse(pKF, Scw, ...) has none
+                const float3 Pc = camera_point(C.Rcw, C.tcw, A.x, A.y, A.z);               // :850-851
+                if (Pc.z < 0.0f) break;                                                    // :854
+                if (!fuse_pinhole(C, C, Pc.x, Pc.y, Pc.z, px)) break;                      // :857-865
                 const float ox = __fsub_rn(A.x, C.Ow[0]), oy = __fsub_rn(A.y, C.Ow[1]), oz = __fsub_rn(A.z, C.Ow[2]);   // :872
-                double sq = __dadd_rn(0.0, __dmul_rn((double)ox, (double)ox));
-                sq = __dadd_rn(sq, __dmul_rn((double)oy, (double)oy));
-                sq = __dadd_rn(sq, __dmul_rn((double)oz, (double)oz));
-                const float dist = (float)__dsqrt_rn(sq);                  // :873 cv::norm
-                if (!(dist > 0.0f) || !isfinite(dist)) break;              // outside the contract
-                if (dist < __fmul_rn(0.8f, A.w) || dist > __fmul_rn(1.2f, N.w)) break;     // :876
-                double dot = __dadd_rn(0.0, __dmul_rn((double)ox, (double)N.x));           // :882 Mat::dot
-                dot = __dadd_rn(dot, __dmul_rn((double)oy, (double)N.y));
-                dot = __dadd_rn(dot, __dmul_rn((double)oz, (double)N.z));
-                if (dot < __dmul_rn(0.5, (double)dist)) break;
-                const float ratio = __fdiv_rn(N.w, dist);                  // src/MapPoint.cc:417-432
-                if (!isfinite(ratio)) break;                               // outside the contract
-                int level = 0;
-                const int nl = min(C.nlevels, 16);
-                for (int k = 0; k < nl - 1; k++) level += ratio >= C.level_ratio[k] ? 1 : 0;
-                q.u = u;
-                q.v = v;
+                const float dist = (float)cv_norm3(ox, oy, oz);                            // :873
+                if (!in_distance_window(dist, A.w, N.w)) break;                            // :876
+                if (mat_dot3(ox, oy, oz, N.x, N.y, N.z) < __dmul_rn(0.5, (double)dist)) break;   // :882
+                int level;
+                if (!predict_scale(C, N.w, dist, level)) break;                            // :886
+                q.u = px.u;
+                q.v = px.v;
                 q.radius = __fmul_rn(C.th, C.scale_factors[level]);        // :888
-                q.proj_xr = ur;
+                q.proj_xr = SIM3 ? 0.0f : __fsub_rn(px.u, __fmul_rn(C.mbf, px.invz));      // :868; Fuse(pKF, Scw, ...) has none
                 q.min_level = level - 1;                                   // :913
                 q.max_level = level;
                 q.flags = ORBHIP_Q_ACTIVE | ORBHIP_Q_OBSERVED;

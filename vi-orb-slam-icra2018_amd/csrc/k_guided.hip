@@ -16,7 +16,8 @@
 //                   accepted in order until a row considered a feature that an earlier row of the group has just
 //                   closed (that row is redone); then the rotation histogram.  A point with more candidates than
 //                   the list holds is rescanned exactly as the reference does it.
-#include "localmap_dev.h"   // GridParams, window_cells, WAVE_LDS_SYNC, window_row_best
+#include "localmap_dev.h"   // GridParams, window_cells, WAVE_LDS_SYNC, chi2_gate, window_row_best
+#include "bow_rot_dev.h"    // BS_HISTO, bow_rot_bin, bow_three_maxima, bow_rot_keeps
 
 #define GCOLS ORBHIP_GRID_COLS
 #define GROWS ORBHIP_GRID_ROWS
@@ -210,7 +211,8 @@ __device__ __forceinline__ void walk_window_rec(const GridParams &gp, const orbh
 }
 
 // QIND (the local-map search, k_localmap.hip): a point's descriptor is row qslot[b][iq] of qdesc -- the resident map-point store --
-// instead of row [b][iq]; a point without a slot is never ORBHIP_Q_ACTIVE.
+// instead of row [b][iq]; a point without a slot is never ORBHIP_Q_ACTIVE.  k_proj_cands, k_proj_cands_row and k_proj_assign exist
+// in both forms; qslot is null, and not read, when QIND is false.
 template <bool QIND>
 __device__ __forceinline__ const uint4 *proj_qdesc(const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ qslot, size_t at)
 {
@@ -219,7 +221,7 @@ __device__ __forceinline__ const uint4 *proj_qdesc(const uint8_t *__restrict__ q
 
 // candidate tuple: distance (9 bits) | octave << 9 (4 bits) | feature index << 13
 template <bool QIND>
-__device__ __forceinline__ void k_proj_cands_body(const orbhip_keypoint *__restrict__ kps,
+__global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__restrict__ kps,
                                                     const uint8_t *__restrict__ desc, int cap,
                                                     const float *__restrict__ uRight, const GridParams gp,
                                                     const int32_t *__restrict__ cellOff,
@@ -256,38 +258,12 @@ __device__ __forceinline__ void k_proj_cands_body(const orbhip_keypoint *__restr
     tcount[(size_t)b * capQpad + iq] = count;
 }
 
-// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
-__global__ __launch_bounds__(256) void k_proj_cands(const orbhip_keypoint *__restrict__ kps,
-                                                    const uint8_t *__restrict__ desc, int cap,
-                                                    const float *__restrict__ uRight, const GridParams gp,
-                                                    const int32_t *__restrict__ cellOff,
-                                                    const float4 *__restrict__ rec,
-                                                    const orbhip_proj_query *__restrict__ queries,
-                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                    int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                    int32_t *__restrict__ tcount)
-{
-    k_proj_cands_body<false>(kps, desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, nullptr);
-}
-__global__ __launch_bounds__(256) void k_proj_cands_slot(const orbhip_keypoint *__restrict__ kps,
-                                                    const uint8_t *__restrict__ desc, int cap,
-                                                    const float *__restrict__ uRight, const GridParams gp,
-                                                    const int32_t *__restrict__ cellOff,
-                                                    const float4 *__restrict__ rec,
-                                                    const orbhip_proj_query *__restrict__ queries,
-                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                    int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                    int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
-{
-    k_proj_cands_body<true>(kps, desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
-}
-
 // The same lists for ONE frame per call: a 16-lane row per point instead of a thread.  A thread walks its window record by
 // record (20-40 dependent trips to memory: 85 us for the 1000 points of a frame, however few of them there are); a row reads
 // the cell ranges of up to 16 window columns at once, flattens them (row prefix sum) and examines 16 records per trip; the
 // records that pass keep their visiting order through a row ballot.  Same tuples, same counts.
 template <bool QIND>
-__device__ __forceinline__ void k_proj_cands_row_body(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
+__global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
                                                         const GridParams gp, const int32_t *__restrict__ cellOff,
                                                         const float4 *__restrict__ rec,
                                                         const orbhip_proj_query *__restrict__ queries,
@@ -354,28 +330,6 @@ __device__ __forceinline__ void k_proj_cands_row_body(const uint8_t *__restrict_
     if (gl == 0) tcount[(size_t)b * capQpad + iq] = count;
 }
 
-// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
-__global__ __launch_bounds__(256) void k_proj_cands_row(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
-                                                        const GridParams gp, const int32_t *__restrict__ cellOff,
-                                                        const float4 *__restrict__ rec,
-                                                        const orbhip_proj_query *__restrict__ queries,
-                                                        const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                        int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                        int32_t *__restrict__ tcount)
-{
-    k_proj_cands_row_body<false>(desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, nullptr);
-}
-__global__ __launch_bounds__(256) void k_proj_cands_row_slot(const uint8_t *__restrict__ desc, int cap, const float *__restrict__ uRight,
-                                                        const GridParams gp, const int32_t *__restrict__ cellOff,
-                                                        const float4 *__restrict__ rec,
-                                                        const orbhip_proj_query *__restrict__ queries,
-                                                        const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                        int capQ, int capQpad, int keff, uint32_t *__restrict__ tuples,
-                                                        int32_t *__restrict__ tcount, const int32_t *__restrict__ qslot)
-{
-    k_proj_cands_row_body<true>(desc, cap, uRight, gp, cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
-}
-
 // ---- per-query best feature of a KeyFrame window: the inner loop of ORBmatcher::Fuse (ref: src/ORBmatcher.cc:887-950 with
 // the chi-square gate on the reprojection error, :1044-1075 without) and of SearchBySim3 (:1190-1224, :1270-1304).  The
 // queries are independent (no feature is closed by an earlier point), so one thread walks one window; the first feature
@@ -413,18 +367,7 @@ __global__ __launch_bounds__(256) void k_window_best(const uint8_t *__restrict__
                     const int w = __float_as_int(r.z), oct = w & 255, idx = w >> 8;
                     if (!(fabsf(__fsub_rn(r.x, q.u)) < q.radius && fabsf(__fsub_rn(r.y, q.v)) < q.radius)) continue;
                     if (oct < q.min_level || oct > q.max_level) continue;
-                    if (gate.on) {
-                        const float ex = __fsub_rn(q.u, r.x), ey = __fsub_rn(q.v, r.y);
-                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        const float ur = UR ? UR[idx] : -1.0f;
-                        double lim = 5.99;
-                        if (ur >= 0) {
-                            const float er = __fsub_rn(q.proj_xr, ur);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            lim = 7.8;
-                        }
-                        if ((double)__fmul_rn(e2, gate.invSigma2[oct & 15]) > lim) continue;
-                    }
+                    if (gate.on && !chi2_gate(q, r.x, r.y, UR ? UR[idx] : -1.0f, gate.invSigma2[oct & 15])) continue;
                     const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
                     if (d < bd) {
                         bd = d;
@@ -470,7 +413,7 @@ __global__ __launch_bounds__(256) void k_window_best_row(const uint8_t *__restri
 }
 
 template <bool QIND>
-__device__ __forceinline__ void k_proj_assign_body(const orbhip_keypoint *__restrict__ kps,
+__global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__restrict__ kps,
                                                     const uint8_t *__restrict__ desc,
                                                     const int32_t *__restrict__ cnt, int cap,
                                                     const float *__restrict__ uRight,
@@ -670,48 +613,17 @@ __device__ __forceinline__ void k_proj_assign_body(const orbhip_keypoint *__rest
         for (int iq = lane; iq < NQ; iq += 64) {
             const int f = qfeat[(size_t)b * capQpad + iq];
             if (f < 0) continue;
-            float rot = __fsub_rn(Q[iq].angle, K[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30) atomicAdd(&s_hist[bin], 1);
+            const int bin = bow_rot_bin(Q[iq].angle, K[f].angle);
+            if (bin >= 0 && bin < BS_HISTO) atomicAdd(&s_hist[bin], 1);
         }
         WAVE_LDS_SYNC();
-        if (lane == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    i3 = i;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                i2 = -1;
-                i3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                i3 = -1;
-            }
-            s_keep[0] = i1;
-            s_keep[1] = i2;
-            s_keep[2] = i3;
-        }
+        if (lane == 0) bow_three_maxima(s_hist, s_keep);
         WAVE_LDS_SYNC();
         int removed = 0;
         for (int iq = lane; iq < NQ; iq += 64) {
             const int f = qfeat[(size_t)b * capQpad + iq];
             if (f < 0) continue;
-            float rot = __fsub_rn(Q[iq].angle, K[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            if (!bow_rot_keeps(bow_rot_bin(Q[iq].angle, K[f].angle), s_keep)) {
                 s_match[f] = -2;   // assigned, then removed: the reference stores NULL here (:1489)
                 removed++;
             }
@@ -721,42 +633,6 @@ __device__ __forceinline__ void k_proj_assign_body(const orbhip_keypoint *__rest
     }
     for (int i = lane; i < cap; i += 64) match[(size_t)b * cap + i] = s_match[i];
     if (lane == 0) nmatches[b] = nm;
-}
-
-// the kernel as it always was, and its twin that reads a point's descriptor from the map-point store by slot
-__global__ __launch_bounds__(64) void k_proj_assign(const orbhip_keypoint *__restrict__ kps,
-                                                    const uint8_t *__restrict__ desc,
-                                                    const int32_t *__restrict__ cnt, int cap,
-                                                    const float *__restrict__ uRight,
-                                                    const uint8_t *__restrict__ occupied, const GridParams gp,
-                                                    const int32_t *__restrict__ cellOff,
-                                                    const int32_t *__restrict__ cellIdx,
-                                                    const orbhip_proj_query *__restrict__ queries,
-                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                    int capQ, int capQpad, int keff, const uint32_t *__restrict__ tuples,
-                                                    const int32_t *__restrict__ tcount, int32_t *__restrict__ qfeat,
-                                                    int use_ratio, float nnratio, int check_ori, int th_high,
-                                                    int32_t *__restrict__ match, int32_t *__restrict__ nmatches,
-                                                    const int32_t *__restrict__ fallback)
-{
-    k_proj_assign_body<false>(kps, desc, cnt, cap, uRight, occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, nullptr);
-}
-__global__ __launch_bounds__(64) void k_proj_assign_slot(const orbhip_keypoint *__restrict__ kps,
-                                                    const uint8_t *__restrict__ desc,
-                                                    const int32_t *__restrict__ cnt, int cap,
-                                                    const float *__restrict__ uRight,
-                                                    const uint8_t *__restrict__ occupied, const GridParams gp,
-                                                    const int32_t *__restrict__ cellOff,
-                                                    const int32_t *__restrict__ cellIdx,
-                                                    const orbhip_proj_query *__restrict__ queries,
-                                                    const uint8_t *__restrict__ qdesc, const int32_t *__restrict__ nq,
-                                                    int capQ, int capQpad, int keff, const uint32_t *__restrict__ tuples,
-                                                    const int32_t *__restrict__ tcount, int32_t *__restrict__ qfeat,
-                                                    int use_ratio, float nnratio, int check_ori, int th_high,
-                                                    int32_t *__restrict__ match, int32_t *__restrict__ nmatches,
-                                                    const int32_t *__restrict__ fallback, const int32_t *__restrict__ qslot)
-{
-    k_proj_assign_body<true>(kps, desc, cnt, cap, uRight, occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, qslot);
 }
 
 // ---- the same assignment for ONE frame per call (a frame or two per launch): parallel fixed point ----------------------
@@ -884,48 +760,17 @@ __global__ __launch_bounds__(1024) void k_proj_assign_par(const orbhip_keypoint 
         for (int iq = tid; iq < NQ; iq += nth) {
             const int f = s_feat[iq];
             if (f < 0) continue;
-            float rot = __fsub_rn(Q[iq].angle, K[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30) atomicAdd(&s_hist[bin], 1);
+            const int bin = bow_rot_bin(Q[iq].angle, K[f].angle);
+            if (bin >= 0 && bin < BS_HISTO) atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    i3 = i;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                i2 = -1;
-                i3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                i3 = -1;
-            }
-            s_keep[0] = i1;
-            s_keep[1] = i2;
-            s_keep[2] = i3;
-        }
+        if (tid == 0) bow_three_maxima(s_hist, s_keep);
         __syncthreads();
         int removed = 0;
         for (int iq = tid; iq < NQ; iq += nth) {
             const int f = s_feat[iq];
             if (f < 0) continue;
-            float rot = __fsub_rn(Q[iq].angle, K[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2]) {
+            if (!bow_rot_keeps(bow_rot_bin(Q[iq].angle, K[f].angle), s_keep)) {
                 s_match[f] = -2;   // assigned, then removed: the reference stores NULL here (:1489)
                 removed++;
             }
@@ -1315,51 +1160,23 @@ __global__ __launch_bounds__(INIT_NT) void k_init_assign(const orbhip_keypoint *
     }
     ORB_ABL_IF(stop == 2) return;
     if (check_ori) {
+        auto bin_of = [&](int i1, int f) {
+            return staged ? bow_rot_bin(s_a1[i1], s_k2[3 * f + 2]) : bow_rot_bin(K1[i1].angle, K2[f].angle);
+        };
         for (int i1 = tid; i1 < n1; i1 += INIT_NT) {
             const int f = s_acc[i1];
             if (f < 0) continue;
-            float rot = staged ? __fsub_rn(s_a1[i1], s_k2[3 * f + 2]) : __fsub_rn(K1[i1].angle, K2[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30) atomicAdd(&s_hist[bin], 1);
+            const int bin = bin_of(i1, f);
+            if (bin >= 0 && bin < BS_HISTO) atomicAdd(&s_hist[bin], 1);
         }
         __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int i = 0; i < 30; i++) {
-                const int s = s_hist[i];
-                if (s > max1) {
-                    max3 = max2; max2 = max1; max1 = s;
-                    i3 = i2; i2 = i1; i1 = i;
-                } else if (s > max2) {
-                    max3 = max2; max2 = s;
-                    i3 = i2; i2 = i;
-                } else if (s > max3) {
-                    max3 = s;
-                    i3 = i;
-                }
-            }
-            if ((float)max2 < 0.1f * (float)max1) {
-                i2 = -1;
-                i3 = -1;
-            } else if ((float)max3 < 0.1f * (float)max1) {
-                i3 = -1;
-            }
-            s_keep[0] = i1;
-            s_keep[1] = i2;
-            s_keep[2] = i3;
-        }
+        if (tid == 0) bow_three_maxima(s_hist, s_keep);
         __syncthreads();
         int removed = 0;
         for (int i1 = tid; i1 < n1; i1 += INIT_NT) {
             const int f = s_acc[i1];
             if (f < 0) continue;
-            float rot = staged ? __fsub_rn(s_a1[i1], s_k2[3 * f + 2]) : __fsub_rn(K1[i1].angle, K2[f].angle);
-            if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-            int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-            if (bin == 30) bin = 0;
-            if (bin >= 0 && bin < 30 && bin != s_keep[0] && bin != s_keep[1] && bin != s_keep[2] && s_m12[i1] >= 0) {
+            if (!bow_rot_keeps(bin_of(i1, f), s_keep) && s_m12[i1] >= 0) {
                 s_m12[i1] = -1;
                 removed++;
             }
@@ -1523,19 +1340,13 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
     hipLaunchKernelGGL(k_proj_records, dim3((cap + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, cap, cellOff, cellIdx, rec);
     static const bool seqOnly = ORB_TUNE("PROJ_SEQ", 0) != 0;
     if (!seqOnly) {   // a 16-lane row per point (written for the single-frame call; 512-frame batches gain 3-4 % from it too)
-        if (qslot)
-            hipLaunchKernelGGL(k_proj_cands_row_slot, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff,
-                               rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
-        else
-            hipLaunchKernelGGL(k_proj_cands_row, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff, rec,
-                               queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
+        const auto cands = qslot ? k_proj_cands_row<true> : k_proj_cands_row<false>;
+        hipLaunchKernelGGL(cands, dim3((capQpad + 15) / 16, B, 1), dim3(256, 1, 1), 0, s, desc, cap, uRight, gp, cellOff, rec, queries,
+                           qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
     } else {
-        if (qslot)
-            hipLaunchKernelGGL(k_proj_cands_slot, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp,
-                               cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
-        else
-            hipLaunchKernelGGL(k_proj_cands, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp,
-                               cellOff, rec, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount);
+        const auto cands = qslot ? k_proj_cands<true> : k_proj_cands<false>;
+        hipLaunchKernelGGL(cands, dim3((capQpad + 255) / 256, B, 1), dim3(256, 1, 1), 0, s, kps, desc, cap, uRight, gp, cellOff, rec,
+                           queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qslot);
     }
     // the parallel fixed-point kernel first; frames it cannot do (a point with more than 32
     // candidates, no fixed point yet) are left to the sequential one through fallback[] (ORBHIP_PROJ_SEQ=1: sequential only)
@@ -1549,20 +1360,11 @@ int launch_search_by_projection(hipStream_t s, const orbhip_keypoint *kps, const
         hipLaunchKernelGGL(k_proj_assign_par, dim3(B, 1, 1), dim3(1024, 1, 1), parLds, s, kps, cnt, cap, occupied, queries, nq, capQ,
                            capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, maxRounds);
     }
-    if (qslot) {
-        if (proj_assign_lds(cap) > 32 * 1024)
-            (void)hipFuncSetAttribute((const void *)k_proj_assign_slot, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)proj_assign_lds(cap));
-        hipLaunchKernelGGL(k_proj_assign_slot, dim3(B, 1, 1), dim3(64, 1, 1), proj_assign_lds(cap), s, kps, desc, cnt, cap, uRight,
-                           occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat,
-                           use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback, qslot);
-        return ORBHIP_OK;
-    }
+    const auto assign = qslot ? k_proj_assign<true> : k_proj_assign<false>;
     if (proj_assign_lds(cap) > 32 * 1024)
-        (void)hipFuncSetAttribute((const void *)k_proj_assign, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)proj_assign_lds(cap));
-    hipLaunchKernelGGL(k_proj_assign, dim3(B, 1, 1), dim3(64, 1, 1), proj_assign_lds(cap), s, kps, desc, cnt, cap, uRight,
-                       occupied, gp, cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat,
-                       use_ratio, nnratio, check_ori, th_high, match, nmatches, fallback);
+        (void)hipFuncSetAttribute((const void *)assign, hipFuncAttributeMaxDynamicSharedMemorySize, (int)proj_assign_lds(cap));
+    hipLaunchKernelGGL(assign, dim3(B, 1, 1), dim3(64, 1, 1), proj_assign_lds(cap), s, kps, desc, cnt, cap, uRight, occupied, gp,
+                       cellOff, cellIdx, queries, qdesc, nq, capQ, capQpad, keff, tuples, tcount, qfeat, use_ratio, nnratio, check_ori,
+                       th_high, match, nmatches, fallback, qslot);
     return ORBHIP_OK;
 }

@@ -7,10 +7,9 @@
 //   k_local_frustum   one lane per local point: gathers its slot, evaluates isInFrustum in the reference's order with the
 //                     reference's roundings, writes the record the reference leaves in the MapPoint and the query of the
 //                     window search (k_guided.hip), which reads the point's descriptor from the store by slot.
-// The arithmetic: every cv::Mat expression as OpenCV 2.4 evaluates it -- the gemm in double with one
-// rounding per component, cv::norm and Mat::dot summed in double -- everything else individually rounded float operations.
-// The scale level is a count over a host-built threshold table (api_localmap.hip) instead of a device logf.
-#include "localmap_dev.h"
+// isInFrustum's own choices between the shared steps (project_dev.h): `PcZ < 0` rejects, invz is a FLOAT division,
+// u = (fx * PcX) * invz + cx, the bounds are closed, and the viewing test compares the rounded cosine with the camera's limit.
+#include "project_dev.h"
 
 __global__ __launch_bounds__(256) void k_map_scatter(const int32_t *__restrict__ slot, const float4 *__restrict__ a,
                                                      const float4 *__restrict__ b, const uint32_t *__restrict__ flags,
@@ -55,7 +54,7 @@ __global__ __launch_bounds__(256) void k_local_frustum(const float4 *__restrict_
         const orbhip_local_camera &C = cams[b];
         const size_t at = (size_t)b * capQ + iq;
         orbhip_local_point rec = {0.f, 0.f, 0.f, 0.f, 0, 0};
-        orbhip_proj_query q = {0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0};
+        orbhip_proj_query q = empty_query();
         const int s = slots[at];
         uint32_t fl = 0;
         if (s >= 0 && s < maxPoints && !skip[at]) fl = mflags[s];
@@ -63,32 +62,20 @@ __global__ __launch_bounds__(256) void k_local_frustum(const float4 *__restrict_
             const float4 A = geoA[s], N = geoB[s];   // {P, mfMinDistance}, {normal, mfMaxDistance}
             do {
                 if (!finite3(A.x, A.y, A.z)) break;   // outside the contract: not in view
-                const float PcX = gemm_row(C.Rcw, C.tcw[0], A.x, A.y, A.z);
-                const float PcY = gemm_row(C.Rcw + 3, C.tcw[1], A.x, A.y, A.z);
-                const float PcZ = gemm_row(C.Rcw + 6, C.tcw[2], A.x, A.y, A.z);
-                if (PcZ < 0.0f) break;                                                     // ref: src/Frame.cc:627
-                const float invz = __fdiv_rn(1.0f, PcZ);
-                const float u = __fadd_rn(__fmul_rn(__fmul_rn(C.fx, PcX), invz), C.cx);    // :632-633
-                const float v = __fadd_rn(__fmul_rn(__fmul_rn(C.fy, PcY), invz), C.cy);
+                const float3 Pc = camera_point(C.Rcw, C.tcw, A.x, A.y, A.z);
+                if (Pc.z < 0.0f) break;                                                    // ref: src/Frame.cc:627
+                const float invz = __fdiv_rn(1.0f, Pc.z);
+                const float u = __fadd_rn(__fmul_rn(__fmul_rn(C.fx, Pc.x), invz), C.cx);   // :632-633
+                const float v = __fadd_rn(__fmul_rn(__fmul_rn(C.fy, Pc.y), invz), C.cy);
                 if (u < C.min_x || u > C.max_x) break;
                 if (v < C.min_y || v > C.max_y) break;
                 const float ox = __fsub_rn(A.x, C.Ow[0]), oy = __fsub_rn(A.y, C.Ow[1]), oz = __fsub_rn(A.z, C.Ow[2]);   // :643
-                double sq = __dadd_rn(0.0, __dmul_rn((double)ox, (double)ox));
-                sq = __dadd_rn(sq, __dmul_rn((double)oy, (double)oy));
-                sq = __dadd_rn(sq, __dmul_rn((double)oz, (double)oz));
-                const float dist = (float)__dsqrt_rn(sq);
-                if (!(dist > 0.0f) || !isfinite(dist)) break;                              // outside the contract
-                if (dist < __fmul_rn(0.8f, A.w) || dist > __fmul_rn(1.2f, N.w)) break;     // :646, src/MapPoint.cc:388-398
-                double dot = __dadd_rn(0.0, __dmul_rn((double)ox, (double)N.x));
-                dot = __dadd_rn(dot, __dmul_rn((double)oy, (double)N.y));
-                dot = __dadd_rn(dot, __dmul_rn((double)oz, (double)N.z));
-                const float viewCos = (float)__ddiv_rn(dot, (double)dist);                 // :652
+                const float dist = (float)cv_norm3(ox, oy, oz);
+                if (!in_distance_window(dist, A.w, N.w)) break;                            // :646
+                const float viewCos = (float)__ddiv_rn(mat_dot3(ox, oy, oz, N.x, N.y, N.z), (double)dist);   // :652
                 if (viewCos < C.viewing_cos_limit) break;
-                const float ratio = __fdiv_rn(N.w, dist);                                  // src/MapPoint.cc:417-432
-                if (!isfinite(ratio)) break;                                               // outside the contract
-                int level = 0;
-                const int nl = min(C.nlevels, 16);   // (a record that orbhip_local_camera_prepare would refuse must not read past the arrays)
-                for (int k = 0; k < nl - 1; k++) level += ratio >= C.level_ratio[k] ? 1 : 0;
+                int level;
+                if (!predict_scale(C, N.w, dist, level)) break;
                 float r = (double)viewCos > 0.998 ? 2.5f : 4.0f;                           // src/ORBmatcher.cc:131-137
                 if (C.th != 1.0f) r = __fmul_rn(r, C.th);                                  // :65-66
                 rec.u = u;
@@ -110,8 +97,7 @@ __global__ __launch_bounds__(256) void k_local_frustum(const float4 *__restrict_
         points[at] = rec;
         queries[at] = q;
     }
-    const unsigned long long m = __ballot(inView);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(nToMatch + b, __popcll(m));
+    count_active(inView, nToMatch + b);
 }
 
 void launch_map_scatter(hipStream_t s, const int32_t *slot, const void *a, const void *b, const uint32_t *flags, const void *desc,

@@ -2,31 +2,26 @@
 //   k_project_last_frame        ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono), ref: src/ORBmatcher.cc:1366-1413
 //   k_project_keyframe_points   ORBmatcher::SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist), ref: :1516-1558
 // One lane per source feature, blockIdx.y = the frame of a batch.  A lane gathers its point from the store's structure of arrays
-// by slot (whole dwordx4 loads), projects it with the arithmetic of host/ORBmatcher.cc's FrameCamera::project -- the camera
-// point is one gemm in double rounded once, the reciprocal depth a DOUBLE division rounded to float (not the float division of
-// isInFrustum), every other operation an individually rounded float operation -- and writes the query of the window search
-// (k_guided.hip), which reads the point's descriptor from the store by slot.  Inactive queries are all zero.  The camera record
-// is indexed by blockIdx.y alone, so it arrives through scalar loads.
+// by slot (whole dwordx4 loads), projects it with the arithmetic of host/ORBmatcher.cc's FrameCamera::project (project_point
+// below; the shared steps are project_dev.h's) and writes the query of the window search (k_guided.hip), which reads the point's
+// descriptor from the store by slot.  Inactive queries are all zero.  The camera record is indexed by blockIdx.y alone, so it
+// arrives through scalar loads.
 // Divergences from the reference, by design (the reference reaches undefined behaviour there): a point with a non-finite
 // position, a non-finite reciprocal depth (z == 0), u or v, dist3D == 0 or non-finite, a non-finite mfMaxDistance / dist3D, or a
 // slot that is not live is inactive; so is a source keypoint whose octave is outside [0, nlevels).
-#include "localmap_dev.h"
+#include "project_dev.h"
 
-struct ProjPixel {
-    float u, v, invz;
-};
-
-// false: outside the image or outside the contract.  *px is what the reference's loop has at that point.
+// The frame searches' pinhole: the reciprocal depth is a DOUBLE division rounded to float (not the float division of isInFrustum
+// and Fuse), u = (fx * xc) * invz + cx, closed bounds.  false: outside the image or outside the contract.  *px is what the
+// reference's loop has at that point.
 __device__ __forceinline__ bool project_point(const orbhip_local_camera &C, const float4 A, ProjPixel *px)
 {
     if (!finite3(A.x, A.y, A.z)) return false;
-    const float xc = gemm_row(C.Rcw, C.tcw[0], A.x, A.y, A.z);
-    const float yc = gemm_row(C.Rcw + 3, C.tcw[1], A.x, A.y, A.z);
-    const float zc = gemm_row(C.Rcw + 6, C.tcw[2], A.x, A.y, A.z);
-    const float invz = (float)__ddiv_rn(1.0, (double)zc);                          // ref: :1381, :1530
+    const float3 Pc = camera_point(C.Rcw, C.tcw, A.x, A.y, A.z);
+    const float invz = (float)__ddiv_rn(1.0, (double)Pc.z);                        // ref: :1381, :1530
     if (!isfinite(invz)) return false;
-    const float u = __fadd_rn(__fmul_rn(__fmul_rn(C.fx, xc), invz), C.cx);         // :1386-1387, :1532-1533
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(C.fy, yc), invz), C.cy);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(C.fx, Pc.x), invz), C.cx);       // :1386-1387, :1532-1533
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(C.fy, Pc.y), invz), C.cy);
     if (!isfinite(u) || !isfinite(v)) return false;
     if (u < C.min_x || u > C.max_x) return false;                                  // :1389-1392, :1535-1538
     if (v < C.min_y || v > C.max_y) return false;
@@ -48,7 +43,7 @@ __global__ __launch_bounds__(256) void k_project_last_frame(const float4 *__rest
     if (iq < NQ) {
         const orbhip_local_camera &C = cams[b];
         const size_t at = (size_t)b * capQ + iq;
-        orbhip_proj_query q = {0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0};
+        orbhip_proj_query q = empty_query();
         const int s = slots[at];                             // -1: no point, an outlier (ref: :1370-1372), a key the store does not know
         uint32_t fl = 0;
         if (s >= 0 && s < maxPoints) fl = mflags[s];
@@ -99,7 +94,7 @@ __global__ __launch_bounds__(256) void k_project_keyframe_points(const float4 *_
     if (iq < min(nq[b], capQ)) {
         const orbhip_local_camera &C = cams[b];
         const size_t at = (size_t)b * capQ + iq;
-        orbhip_proj_query q = {0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0};
+        orbhip_proj_query q = empty_query();
         int s = -1;
         if (iq < NQ) s = kf_entry_slot(row[1 + iq], mflags, maxPoints);    // live, not bad, the entry's generation (:1520-1522)
         if (s >= 0 && marks[s] == 0u) {                                    // sAlreadyFound (:1522)
@@ -108,17 +103,10 @@ __global__ __launch_bounds__(256) void k_project_keyframe_points(const float4 *_
             do {
                 if (!project_point(C, A, &px)) break;                      // (no depth-sign test here, as in the reference)
                 const float ox = __fsub_rn(A.x, C.Ow[0]), oy = __fsub_rn(A.y, C.Ow[1]), oz = __fsub_rn(A.z, C.Ow[2]);   // :1541
-                double sq = __dadd_rn(0.0, __dmul_rn((double)ox, (double)ox));
-                sq = __dadd_rn(sq, __dmul_rn((double)oy, (double)oy));
-                sq = __dadd_rn(sq, __dmul_rn((double)oz, (double)oz));
-                const float dist = (float)__dsqrt_rn(sq);                  // :1542 cv::norm
-                if (!(dist > 0.0f) || !isfinite(dist)) break;              // outside the contract
-                if (dist < __fmul_rn(0.8f, A.w) || dist > __fmul_rn(1.2f, N.w)) break;     // :1548-1549
-                const float ratio = __fdiv_rn(N.w, dist);                  // src/MapPoint.cc:417-432
-                if (!isfinite(ratio)) break;                               // outside the contract
-                int level = 0;
-                const int nl = min(C.nlevels, 16);
-                for (int k = 0; k < nl - 1; k++) level += ratio >= C.level_ratio[k] ? 1 : 0;
+                const float dist = (float)cv_norm3(ox, oy, oz);            // :1542
+                if (!in_distance_window(dist, A.w, N.w)) break;            // :1548-1549
+                int level;
+                if (!predict_scale(C, N.w, dist, level)) break;            // :1553
                 q.u = px.u;
                 q.v = px.v;
                 q.radius = __fmul_rn(C.th, C.scale_factors[level]);        // :1555

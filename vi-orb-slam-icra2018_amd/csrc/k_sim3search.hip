@@ -14,9 +14,8 @@
 // The window search between the two is k_window_best_sets<false> (k_fuse.hip) with two target records: direction 0 searches set 2,
 // direction 1 set 1.
 // Divergences from the reference, by design, as k_project_fuse: dist3D == 0 or not finite, a non-finite mfMaxDistance / dist3D and
-// an entry that does not resolve are inactive.  z == 0 (either sign) passes `< 0.0`, u or v is then infinite or NaN and fails
-// IsInImage, as in the reference.
-#include "localmap_dev.h"
+// an entry that does not resolve are inactive.
+#include "project_dev.h"
 
 #include <cstring>
 
@@ -47,39 +46,25 @@ __global__ __launch_bounds__(256) void k_project_sim3(const float4 *__restrict__
     bool active = false;
     if (iq < capQ) {
         const size_t at = (size_t)b * capQ + iq;
-        orbhip_proj_query q = {0.f, 0.f, 0.f, 0.f, 0, 0, 0.f, 0};
+        orbhip_proj_query q = empty_query();
         int s = -1;
         if (iq < NQ) s = kf_entry_slot(row[1 + iq], mflags, maxPoints);    // !pMP, isBad() (ref: :1152-1156)
         bool take = s >= 0;
         if (take && taken) take = taken[iq] == 0;                          // vbAlreadyMatched (:1152, :1232)
         if (take) {
             const float4 A = geoA[s], N = geoB[s];                         // {P, mfMinDistance}, {normal, mfMaxDistance}
+            ProjPixel px;
             do {
-                const float x1 = gemm_row(S.Rcw, S.tcw[0], A.x, A.y, A.z); // :1159 / :1239
-                const float y1 = gemm_row(S.Rcw + 3, S.tcw[1], A.x, A.y, A.z);
-                const float z1 = gemm_row(S.Rcw + 6, S.tcw[2], A.x, A.y, A.z);
-                const float xc = gemm_row(P.sR[b], P.t[b][0], x1, y1, z1); // :1160 / :1240
-                const float yc = gemm_row(P.sR[b] + 3, P.t[b][1], x1, y1, z1);
-                const float zc = gemm_row(P.sR[b] + 6, P.t[b][2], x1, y1, z1);
-                if (zc < 0.0f) break;                                      // :1163
-                const float invz = __fdiv_rn(1.0f, zc);                    // :1166 (a float division)
-                const float x = __fmul_rn(xc, invz), y = __fmul_rn(yc, invz);
-                const float u = __fadd_rn(__fmul_rn(K1.fx, x), K1.cx);     // :1170-1171: key frame 1's intrinsics, both ways
-                const float v = __fadd_rn(__fmul_rn(K1.fy, y), K1.cy);
-                if (!(u >= D.min_x && u < D.max_x && v >= D.min_y && v < D.max_y)) break;   // :1174, src/KeyFrame.cc IsInImage
-                double sq = __dadd_rn(0.0, __dmul_rn((double)xc, (double)xc));
-                sq = __dadd_rn(sq, __dmul_rn((double)yc, (double)yc));
-                sq = __dadd_rn(sq, __dmul_rn((double)zc, (double)zc));
-                const float dist = (float)__dsqrt_rn(sq);                  // :1179 cv::norm of the camera point
-                if (!(dist > 0.0f) || !isfinite(dist)) break;              // outside the contract
-                if (dist < __fmul_rn(0.8f, A.w) || dist > __fmul_rn(1.2f, N.w)) break;     // :1182
-                const float ratio = __fdiv_rn(N.w, dist);                  // src/MapPoint.cc:417-432
-                if (!isfinite(ratio)) break;                               // outside the contract
-                int level = 0;
-                const int nl = min(D.nlevels, 16);
-                for (int k = 0; k < nl - 1; k++) level += ratio >= D.level_ratio[k] ? 1 : 0;
-                q.u = u;
-                q.v = v;
+                const float3 P1 = camera_point(S.Rcw, S.tcw, A.x, A.y, A.z);               // :1159 / :1239
+                const float3 Pc = camera_point(P.sR[b], P.t[b], P1.x, P1.y, P1.z);         // :1160 / :1240
+                if (Pc.z < 0.0f) break;                                                    // :1163
+                if (!fuse_pinhole(K1, D, Pc.x, Pc.y, Pc.z, px)) break;     // :1166-1174: key frame 1's intrinsics, both ways
+                const float dist = (float)cv_norm3(Pc.x, Pc.y, Pc.z);      // :1179: of the camera point
+                if (!in_distance_window(dist, A.w, N.w)) break;            // :1182
+                int level;
+                if (!predict_scale(D, N.w, dist, level)) break;            // :1186
+                q.u = px.u;
+                q.v = px.v;
                 q.radius = __fmul_rn(P.th, D.scale_factors[level]);        // :1189
                 q.min_level = level - 1;                                   // :1207
                 q.max_level = level;

@@ -1,7 +1,9 @@
-// localmap_dev.h -- device helpers shared by the kernels that read the resident map-point store (k_localmap.hip,
-// k_localcollect.hip, k_covis.hip, k_cull.hip, k_baproblem.hip, k_projtrack.hip, k_fuse.hip, k_loopfuse.hip, k_sim3search.hip, k_bowcand.hip and k_hamming.hip through bow_match_dev.h) and by the window searches (k_guided.hip, k_fuse.hip): the
-// flag-word rules, the reference's gemm, the key-frame row entry, the per-batch count of active queries, the cell window of
-// GetFeaturesInArea and the 16-lane window walk that k_window_best_row and k_window_best_sets share.
+// localmap_dev.h -- device helpers shared by the kernels that read the resident map-point store (k_localcollect.hip, k_covis.hip,
+// k_cull.hip, k_baproblem.hip, k_loopfuse.hip; k_localmap.hip, k_projtrack.hip, k_fuse.hip and k_sim3search.hip through
+// project_dev.h, k_refresh.hip and k_correct.hip through refresh_dev.h, k_bowcand.hip and k_hamming.hip through bow_match_dev.h) and by the
+// window searches (k_guided.hip, k_fuse.hip): the flag-word rules, the reference's gemm, the key-frame row entry, the per-batch
+// count of active queries, the cell window of GetFeaturesInArea, the chi-square gate that k_window_best and window_row_best share
+// and the 16-lane window walk that k_window_best_row and k_window_best_sets share.  The steps of a projection are project_dev.h's.
 #ifndef ORBHIP_LOCALMAP_DEV_H
 #define ORBHIP_LOCALMAP_DEV_H
 #include "orbhip_internal.h"
@@ -63,11 +65,26 @@ __device__ __forceinline__ bool window_cells(const GridParams &gp, float x, floa
     return true;
 }
 
+// The chi-square gate of Fuse's window loop on the reprojection error of the feature at (x, y) (ref: src/ORBmatcher.cc:915-934):
+// e2 * invSigma2 <= 5.99, or <= 7.8 with the right coordinate when the feature has one (ur >= 0; pass a negative value for none).
+// Individually rounded float operations; the float product is compared as a double.
+__device__ __forceinline__ bool chi2_gate(const orbhip_proj_query &q, float x, float y, float ur, float invSigma2)
+{
+    const float ex = __fsub_rn(q.u, x), ey = __fsub_rn(q.v, y);
+    float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+    double lim = 5.99;
+    if (ur >= 0) {
+        const float er = __fsub_rn(q.proj_xr, ur);
+        e2 = __fadd_rn(e2, __fmul_rn(er, er));
+        lim = 7.8;
+    }
+    return !((double)__fmul_rn(e2, invSigma2) > lim);
+}
+
 // One 16-lane row walks the window [x0, x1] x [y0, y1] of one point (ref: src/ORBmatcher.cc:887-950): the cells' runs of the
 // grid-ordered records R are laid end to end through a row scan, lane gl takes every 16th feature.  The geometric filter, the
-// level window, the chi-square gate on the reprojection error (5.99, or 7.8 with the right coordinate when UR[idx] >= 0; the float
-// product compared as a double) and the Hamming distance to (a0, a1).  key = the lane's smallest (distance << 20 | position in
-// visiting order), idx = that feature.  sStart[16], sExcl[17]: the row's LDS.  Row-uniform control flow.
+// level window, the chi-square gate (chi2_gate, with UR[idx] when there is a UR) and the Hamming distance to (a0, a1).
+// key = the lane's smallest (distance << 20 | position in visiting order), idx = that feature.  sStart[16], sExcl[17]: the row's LDS.  Row-uniform control flow.
 template <typename SIGMA>
 __device__ __forceinline__ void window_row_best(const orbhip_proj_query &q, int x0, int x1, int y0, int y1, const uint4 a0,
                                                 const uint4 a1, const uint4 *__restrict__ D, const float *__restrict__ UR,
@@ -93,18 +110,7 @@ __device__ __forceinline__ void window_row_best(const orbhip_proj_query &q, int 
             const int w = __float_as_int(rr.z), oct = w & 255, idx = w >> 8;
             if (!(fabsf(__fsub_rn(rr.x, q.u)) < q.radius && fabsf(__fsub_rn(rr.y, q.v)) < q.radius)) continue;
             if (oct < q.min_level || oct > q.max_level) continue;
-            if (gateOn) {
-                const float ex = __fsub_rn(q.u, rr.x), ey = __fsub_rn(q.v, rr.y);
-                float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                const float ur = UR ? UR[idx] : -1.0f;
-                double lim = 5.99;
-                if (ur >= 0) {
-                    const float er = __fsub_rn(q.proj_xr, ur);
-                    e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                    lim = 7.8;
-                }
-                if ((double)__fmul_rn(e2, invSigma2(oct)) > lim) continue;
-            }
+            if (gateOn && !chi2_gate(q, rr.x, rr.y, UR ? UR[idx] : -1.0f, invSigma2(oct))) continue;
             const int d = hamming256(a0, a1, D[2 * idx], D[2 * idx + 1]);
             const int k = (d << 20) | (seen + r);
             if (d < 256 && k < key) {

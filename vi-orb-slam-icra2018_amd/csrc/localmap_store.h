@@ -1,6 +1,8 @@
 // localmap_store.h -- the host side of the resident map-point store and of the key-frame table, shared by the api_*.hip files
-// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip, api_sim3search.hip, api_cull.hip, api_baproblem.hip): device blocks, the key -> slot / key -> row
-// tables, what a call over several rows of the table (the ordered union) sets up, and the target records of the Fuse calls.
+// that search them (api_localmap.hip, api_projtrack.hip, api_fuse.hip, api_loopfuse.hip, api_sim3search.hip, api_refresh.hip,
+// api_correct.hip, api_covis.hip, api_cull.hip, api_baproblem.hip, api_bowcand.hip): device blocks, the key -> slot / key -> row
+// tables, what a call over several rows of the table (the ordered union) sets up and how it ends, and the target records and
+// cameras of the Fuse calls (api_fuse.hip, api_loopfuse.hip, api_sim3search.hip).
 #ifndef ORBHIP_LOCALMAP_STORE_H
 #define ORBHIP_LOCALMAP_STORE_H
 #include "api_common.h"
@@ -99,11 +101,12 @@ static inline int kf_call_scratch(orbhip_ctx *c, OrbKfTable *K, KfCall &Q, int c
     return ORBHIP_OK;
 }
 
-// ---- the K target key frames of a Fuse call (api_fuse.hip, api_loopfuse.hip) ----
+// ---- the K target key frames of a Fuse call (api_fuse.hip, api_loopfuse.hip, api_sim3search.hip) ----
 #define FUSE_MAX_QUERIES ((int64_t)1 << 24)   // K * n of one call
 #define FUSE_MAX_TARGETS 65535                // one target per blockIdx.y
 #define FUSE_MAX_SET (1 << 20)                // features of a target set: the row kernel keeps a position in 20 bits
 
+// the per-level tables of a camera record are usable (the frame searches of api_projtrack.hip ask the same)
 static inline bool fuse_camera_ok(const orbhip_local_camera *cam) { return cam->nlevels >= 1 && cam->nlevels <= 16 && std::isfinite(cam->th); }
 
 // the K target records of a call, the scratch for their grid-ordered feature records carved behind `recBase`
@@ -135,6 +138,46 @@ static inline int fuse_targets_resolve(orbhip_ctx *c, const char *who, const orb
         T.urTotal += (size_t)T.view[k].n;
         T.maxN = std::max(T.maxN, T.view[k].n);
     }
+    return ORBHIP_OK;
+}
+
+// cams [K] = the targets' cameras as the projection kernels read them: copied, level_ratio filled (orbhip_local_camera_prepare)
+static inline int fuse_cameras_prepare(orbhip_ctx *c, const orbhip_fuse_target *targets, int K, orbhip_local_camera *cams)
+{
+    for (int k = 0; k < K; k++) {
+        cams[k] = targets[k].cam;
+        int rc;
+        if ((rc = orbhip_local_camera_prepare(c, &cams[k]))) return rc;
+    }
+    return ORBHIP_OK;
+}
+
+// The K records of k_fuse_records and k_window_best_sets in the call's packed block; returns their device twin.  Target k's
+// grid-ordered feature records go to recBase + T.recOff[k]; targets[k].inv_level_sigma2 is its gate table; d_uRight = the targets'
+// mvuRight one after the other on the device, each as long as its set, or null.
+static inline const void *fuse_targets_pack(Packed &P, const FuseTargets &T, uint8_t *recBase, const orbhip_fuse_target *targets,
+                                            const float *d_uRight)
+{
+    const size_t tb = fuse_target_bytes();
+    uint8_t *htab;
+    const void *dtab = P.in_reserve(T.view.size() * tb, (void **)&htab);
+    size_t urAt = 0;
+    for (size_t k = 0; k < T.view.size(); k++) {
+        const OrbSetView &S = T.view[k];
+        fuse_target_fill(htab + k * tb, S.d_kps, S.d_desc, S.d_cellOff, S.d_cellIdx, recBase + T.recOff[k], d_uRight ? d_uRight + urAt : nullptr,
+                         S.minX, S.minY, S.invW, S.invH, S.n, targets[k].inv_level_sigma2);
+        urAt += (size_t)S.n;
+    }
+    return dtab;
+}
+
+// The tail of a collect: the keys of the slots that came back (0 for one the store does not hold), then ORBHIP_E_CAPACITY with the
+// caller's message when there were more than cap.  capQ = min(candidates of the call, cap) slots were written.
+static inline int collect_keys_out(orbhip_ctx *c, const OrbLocalMap *M, const int32_t *slots, int got, int capQ, int cap, uint64_t *keys_out,
+                                   const std::string &tooMany)
+{
+    for (int i = 0; i < std::min(got, capQ); i++) keys_out[i] = (slots[i] >= 0 && slots[i] < M->maxPoints) ? M->slotKey[slots[i]] : 0;
+    if (got > cap) return fail(c, ORBHIP_E_CAPACITY, tooMany);
     return ORBHIP_OK;
 }
 

@@ -4,15 +4,7 @@
 // observer at list position j.  Every float / double operation is individually rounded (docs/parity.md, "UpdateNormalAndDepth").
 #ifndef ORBHIP_REFRESH_DEV_H
 #define ORBHIP_REFRESH_DEV_H
-#include "localmap_dev.h"
-
-// cv::norm(NORM_L2) of a CV_32F 3-vector: squares summed in double, the root in double
-__device__ __forceinline__ double norm3(float x, float y, float z)
-{
-    double sq = __dadd_rn(__dmul_rn((double)x, (double)x), __dmul_rn((double)y, (double)y));
-    sq = __dadd_rn(sq, __dmul_rn((double)z, (double)z));
-    return __dsqrt_rn(sq);
-}
+#include "project_dev.h"   // cv_norm3
 
 // The point at (px, py, pz) with N > 0 observers; lane = 0..15 of the row, every lane of the row arrives.  refPos = the position of
 // mpRefKF in the list, level = the octave of its feature.  Each lane forms its observers' scaled viewing directions; the running sum
@@ -30,7 +22,7 @@ __device__ __forceinline__ void normal_and_depth(float px, float py, float pz, i
             float ox, oy, oz;
             centre(i, ox, oy, oz);
             const float dx = __fsub_rn(px, ox), dy = __fsub_rn(py, oy), dz = __fsub_rn(pz, oz);
-            const float a = (float)__ddiv_rn(1.0, norm3(dx, dy, dz));   // normali / norm: a MatExpr scaled by 1.0 / norm
+            const float a = (float)__ddiv_rn(1.0, cv_norm3(dx, dy, dz));   // normali / norm: a MatExpr scaled by 1.0 / norm
             tx = __fmul_rn(dx, a), ty = __fmul_rn(dy, a), tz = __fmul_rn(dz, a);
         }
         const int m = min(16, N - i0);
@@ -43,7 +35,7 @@ __device__ __forceinline__ void normal_and_depth(float px, float py, float pz, i
     const float invN = (float)__ddiv_rn(1.0, (double)N);
     float rx, ry, rz;
     centre(min(max(refPos, 0), N - 1), rx, ry, rz);
-    const float dist = (float)norm3(__fsub_rn(px, rx), __fsub_rn(py, ry), __fsub_rn(pz, rz));
+    const float dist = (float)cv_norm3(__fsub_rn(px, rx), __fsub_rn(py, ry), __fsub_rn(pz, rz));
     const int lv = min(max(level, 0), ORBHIP_MAX_LEVELS - 1);
     const int top = min(max(prm->nlevels - 1, 0), ORBHIP_MAX_LEVELS - 1);
     B.x = __fmul_rn(nx, invN), B.y = __fmul_rn(ny, invN), B.z = __fmul_rn(nz, invN);

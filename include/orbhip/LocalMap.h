@@ -24,6 +24,7 @@
 #endif
 
 struct orbhip_ctx;
+struct orbhip_bow_candidate;
 
 #ifndef ORBHIP_WITH_REFERENCE_HEADERS
 #ifndef ORBHIP_CVLITE_POINT3F
@@ -358,20 +359,39 @@ protected:
     bool EnsureKeyFrames();
     bool VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, KeyFrame *&pReferenceKF);
     bool CollectKeys(const std::vector<KeyFrame *> &vpKFs, std::vector<uint64_t> &kfKeys);
+    // ---- the steps the LocalMap*.cc files share, one definition each, all with mMutex held ----
+    // The store's side (LocalMap.cc): key -> object or NULL; was the point Put; was every non-NULL, non-bad point of the list (else
+    // its key frame goes the host way); keys -> objects element for element; keys and flags of these points in one call.
+    MapPoint *PointOf(uint64_t key) const;
+    bool Known(MapPoint *pMP) const;
+    bool AllKnown(const std::vector<MapPoint *> &vpMPs) const;
+    void PointsOf(const uint64_t *keys, int n, std::vector<MapPoint *> &out) const;
+    bool UpdateFlagsLocked(MapPoint *const *points, size_t n, const char *who);
+    static void AssignNormalDepth(MapPoint *pMP, const float *nrm, float minDistance, float maxDistance);   // a member: the reference protects all three
+    // The table's side (LocalMapCollect.cc).  A row is a key frame's when the table holds one under its key AND for this object: two
+    // live KeyFrame objects never share an mnId, since the device row is addressed by mnId + 1 whatever the host map says.
+    KeyFrame *KeyFrameOf(uint64_t key) const;
+    bool HasRow(KeyFrame *pKF) const;
+    bool EnsureRow(KeyFrame *pKF) { return HasRow(pKF) || PutKeyFrameLocked(pKF); }
+    bool EraseKeyFrameLocked(KeyFrame *pKF, const char *who);     // false: there is no table, nothing was done
     // Fuse's apply loop over one target (ref: src/ORBmatcher.cc:951-972) and the resident state behind it (LocalMapFuse.cc)
     struct FuseEdits {
         std::set<MapPoint *> put, flags;
         std::map<MapPoint *, std::vector<unsigned char> > survivors; // of a Replace: the descriptor each had at the device call
         std::set<std::pair<KeyFrame *, size_t> > entries;           // (key frame, feature) whose row entry may have changed
+        void Remember(MapPoint *surv);                              // keeps a survivor's descriptor, once
+        bool ChangedSince(MapPoint *pMP) const;                     // a survivor whose descriptor differs from the remembered one
+        void Replace(MapPoint *dead, MapPoint *surv);               // dead->Replace(surv), noting the rows, flags and put it dirties
     };
     int ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMPs, const int32_t *bestIdx, const int32_t *bestDist, FuseEdits &edits);
     bool FlushFuse(FuseEdits &edits);
     typedef std::map<uint64_t, std::pair<std::vector<int32_t>, std::vector<uint64_t> > > FuseRows;
-    bool FlushFusePoints(FuseEdits &edits);                       // the store's half of FlushFuse
-    void FuseRowEdits(const FuseEdits &edits, FuseRows &rows);    // the table's half, as lists per key frame
+    bool TakeFuseEdits(FuseEdits &edits, FuseRows &rows);         // what the two flushes share: the store's half, the table's as lists
     bool FlushLoop(FuseEdits &edits);                             // FlushFuse with one orbhip_map_kf_set_batch (LocalMapLoop.cc)
     bool EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey);
     bool ResidentKeyFrame(KeyFrame *pKF, uint64_t *setKey);       // SearchByBoWCandidates: row and set of a key frame the store knows (LocalMapBowCand.cc)
+    void SortCandidates(const std::vector<KeyFrame *> &vpKFs, bool device, std::vector<int> &way, std::vector<orbhip_bow_candidate> &cand,
+                        std::vector<size_t> &who);                // SearchByBoWCandidates: which way each candidate goes
     bool BuildBALocked(const std::vector<KeyFrame *> &vpLocalKFs, unsigned long nStamp, BAProblem &out);   // LocalMapBA.cc
 
     orbhip_ctx *mpCtx;

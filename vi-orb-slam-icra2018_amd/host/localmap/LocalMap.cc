@@ -83,13 +83,54 @@ bool LocalMapSearch::PutLocked(const std::vector<MapPoint *> &vpMPs)
     return true;
 }
 
+MapPoint *LocalMapSearch::PointOf(uint64_t key) const
+{
+    const std::unordered_map<uint64_t, MapPoint *>::const_iterator it = mPointOf.find(key);
+    return it == mPointOf.end() ? static_cast<MapPoint *>(NULL) : it->second;
+}
+
+bool LocalMapSearch::Known(MapPoint *pMP) const { return mPointOf.count(key_of(pMP)) != 0; }
+
+bool LocalMapSearch::AllKnown(const std::vector<MapPoint *> &vpMPs) const
+{
+    for (size_t i = 0; i < vpMPs.size(); i++)
+        if (vpMPs[i] && !vpMPs[i]->isBad() && !Known(vpMPs[i])) return false;
+    return true;
+}
+
+void LocalMapSearch::PointsOf(const uint64_t *keys, int n, std::vector<MapPoint *> &out) const
+{
+    out.assign(n > 0 ? n : 0, static_cast<MapPoint *>(NULL));
+    for (int k = 0; k < n; k++) out[k] = PointOf(keys[k]);
+}
+
+bool LocalMapSearch::UpdateFlagsLocked(MapPoint *const *points, size_t n, const char *who)
+{
+    if (n == 0) return true;
+    uint64_t key1;   // one point (UpdateFlags, once per AddObservation) takes no allocation
+    uint8_t fl1;
+    std::vector<uint64_t> keys(n > 1 ? n : 0);
+    std::vector<uint8_t> fls(keys.size());
+    uint64_t *k = n > 1 ? keys.data() : &key1;
+    uint8_t *f = n > 1 ? fls.data() : &fl1;
+    for (size_t i = 0; i < n; i++) k[i] = key_of(points[i]), f[i] = flags_of(points[i]);
+    if (orbhip_map_update_flags(mpCtx, (int)n, k, f) != ORBHIP_OK) return hipdetail::Fail(who, orbhip_last_error(mpCtx));
+    return true;
+}
+
+void LocalMapSearch::AssignNormalDepth(MapPoint *pMP, const float *nrm, float minDistance, float maxDistance)
+{
+    cv::Mat n(3, 1, CV_32F);
+    for (int c = 0; c < 3; c++) n.at<float>(c, 0) = nrm[c];
+    pMP->mNormalVector = n;
+    pMP->mfMinDistance = minDistance, pMP->mfMaxDistance = maxDistance;
+}
+
 void LocalMapSearch::UpdateFlags(MapPoint *pMP)
 {
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx) return;
-    const uint64_t key = key_of(pMP);
-    const uint8_t fl = flags_of(pMP);
-    if (orbhip_map_update_flags(mpCtx, 1, &key, &fl) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::UpdateFlags", orbhip_last_error(mpCtx));
+    UpdateFlagsLocked(&pMP, 1, "LocalMapSearch::UpdateFlags");
 }
 
 void LocalMapSearch::Erase(MapPoint *pMP)
@@ -118,7 +159,7 @@ int LocalMapSearch::SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &v
     if (!mpCtx) return 0;
     const int n = F.N, nq = (int)vpLocalMapPoints.size();
     if (nq == 0) return 0;
-    if (F.mnScaleLevels < 1 || F.mnScaleLevels > 16 || (int)F.mvScaleFactors.size() < F.mnScaleLevels)
+    if (!localmapdetail::has_pyramid(F))
         return hipdetail::Fail("LocalMapSearch::SearchLocalPoints", "the frame has no scale pyramid (mnScaleLevels, mvScaleFactors)"), 0;
 
     uint64_t frameKey = 0;
@@ -127,13 +168,12 @@ int LocalMapSearch::SearchLocalPoints(Frame &F, const std::vector<MapPoint *> &v
     localmapdetail::fill_camera(F, th, viewingCosLimit, &cam);
 
     std::vector<uint64_t> keys(nq);
-    std::vector<uint8_t> skip(nq), occupied(n > 0 ? n : 1, 0);
+    std::vector<uint8_t> skip(nq), occupied;
     for (int k = 0; k < nq; k++) {
         keys[k] = key_of(vpLocalMapPoints[k]);
         skip[k] = vpLocalMapPoints[k]->mnLastFrameSeen == F.mnId ? 1 : 0;     // ref: src/Tracking.cc:2342
     }
-    for (int i = 0; i < n; i++)
-        if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->Observations() > 0) occupied[i] = 1;   // ref: src/ORBmatcher.cc:87-89
+    localmapdetail::fill_occupied(F, occupied);
     std::vector<orbhip_local_point> pts(nq);
     std::vector<int32_t> match(n > 0 ? n : 1);
     int ntm = 0, found = 0;

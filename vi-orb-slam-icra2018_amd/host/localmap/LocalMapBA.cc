@@ -52,9 +52,8 @@ bool LocalMapSearch::BuildBALocked(const std::vector<KeyFrame *> &vpLocal, unsig
     std::vector<uint64_t> kfKeys(nkf);
     size_t mostPoints = 0;
     for (int k = 0; k < nkf; k++) {
-        std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key_of(vpLocal[k]));
-        if (it == mKeyFrameOf.end() || it->second != vpLocal[k]) return false;   // a local key frame without a row: the caller's loops
-        kfKeys[k] = it->first;
+        if (!HasRow(vpLocal[k])) return false;   // a local key frame without a row: the caller's loops (tests, does not put)
+        kfKeys[k] = key_of(vpLocal[k]);
         mostPoints += (size_t)std::max(vpLocal[k]->N, 0);
     }
     // room: no call has more points than the local rows have features; edges and fixed key frames about as many as last time, and
@@ -65,6 +64,7 @@ bool LocalMapSearch::BuildBALocked(const std::vector<KeyFrame *> &vpLocal, unsig
     std::vector<uint64_t> ptKeys, fixedKeys;
     std::vector<int32_t> off;
     std::vector<orbhip_ba_edge> edges;
+    // not call_with_room: three capacities, each raised to what the call reported, and one second call at the most
     for (int round = 0;; round++) {
         ptKeys.resize(capP > 0 ? capP : 1), fixedKeys.resize(capF > 0 ? capF : 1), off.resize((size_t)capP + 1), edges.resize(capE > 0 ? capE : 1);
         const int rc = orbhip_map_ba_problem(mpCtx, nkf, kfKeys.data(), ptKeys.data(), capP, &np, off.data(), edges.data(), capE, &ne,
@@ -83,14 +83,12 @@ bool LocalMapSearch::BuildBALocked(const std::vector<KeyFrame *> &vpLocal, unsig
     P.vpLocalKFs = vpLocal;
     P.vpLocalMPs.resize(np), P.vpFixedKFs.resize(nf), P.vEdges.resize(ne);
     for (int j = 0; j < np; j++) {
-        std::unordered_map<uint64_t, MapPoint *>::const_iterator it = mPointOf.find(ptKeys[j]);
-        if (it == mPointOf.end()) return hipdetail::Fail(who, "a point of the store without its object");
-        P.vpLocalMPs[j] = it->second;
+        P.vpLocalMPs[j] = PointOf(ptKeys[j]);
+        if (!P.vpLocalMPs[j]) return hipdetail::Fail(who, "a point of the store without its object");
     }
     for (int r = 0; r < nf; r++) {
-        std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(fixedKeys[r]);
-        if (it == mKeyFrameOf.end()) return hipdetail::Fail(who, "a row of the table without its key frame");
-        P.vpFixedKFs[r] = it->second;
+        P.vpFixedKFs[r] = KeyFrameOf(fixedKeys[r]);
+        if (!P.vpFixedKFs[r]) return hipdetail::Fail(who, "a row of the table without its key frame");
     }
     for (int e = 0; e < ne; e++) {
         const int kf = edges[e].kf;

@@ -42,12 +42,28 @@ bool LocalMapSearch::ResidentKeyFrame(KeyFrame *pKF, uint64_t *setKey)
 {
     const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
     if ((int)vpMPs.size() != pKF->mDescriptors.rows || vpMPs.empty()) return false;
-    for (size_t i = 0; i < vpMPs.size(); i++)
-        if (vpMPs[i] && !vpMPs[i]->isBad() && !mPointOf.count(key_of(vpMPs[i]))) return false;
-    std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key_of(pKF));
-    if ((it == mKeyFrameOf.end() || it->second != pKF) && !PutKeyFrameLocked(pKF)) return false;
+    if (!AllKnown(vpMPs) || !EnsureRow(pKF)) return false;
     if (!EnsureFuseSet(pKF, setKey)) return hipdetail::Fail("LocalMapSearch::SearchByBoWCandidates (key frame set)", orbhip_last_error(mpCtx)), false;
     return true;
+}
+
+// Which way each candidate goes: -2 nothing to do (NULL or bad; ref: src/Tracking.cc:2598-2599), -1 the host way (no device, or the
+// table cannot speak for it), >= 0 its place among the device candidates, where who[place] is its index in the caller's vector.
+void LocalMapSearch::SortCandidates(const std::vector<KeyFrame *> &vpKFs, bool device, std::vector<int> &way,
+                                    std::vector<orbhip_bow_candidate> &cand, std::vector<size_t> &who)
+{
+    way.assign(vpKFs.size(), -1);
+    for (size_t k = 0; k < vpKFs.size(); k++) {
+        uint64_t setKey = 0;
+        if (!vpKFs[k] || vpKFs[k]->isBad())
+            way[k] = -2;
+        else if (device && ResidentKeyFrame(vpKFs[k], &setKey)) {
+            way[k] = (int)cand.size();
+            const orbhip_bow_candidate c = {setKey, key_of(vpKFs[k])};
+            cand.push_back(c);
+            who.push_back(k);
+        }
+    }
 }
 
 void LocalMapSearch::SearchByBoWCandidates(const std::vector<KeyFrame *> &vpCandidateKFs, Frame &F,
@@ -60,8 +76,7 @@ void LocalMapSearch::SearchByBoWCandidates(const std::vector<KeyFrame *> &vpCand
     vnMatches.assign(K, 0);
     if (pvSetups) pvSetups->assign(K, RelocCorrespondences());
 
-    // which way each candidate goes: -2 nothing to do (bad), -1 the host way, >= 0 its place among the device candidates
-    std::vector<int> way(K, -1);
+    std::vector<int> way;
     std::vector<orbhip_bow_candidate> cand;
     std::vector<size_t> who;
     const bool gather = pvSetups != 0;
@@ -72,19 +87,7 @@ void LocalMapSearch::SearchByBoWCandidates(const std::vector<KeyFrame *> &vpCand
         hipdetail::Fail("LocalMapSearch::SearchByBoWCandidates (frame set)", orbhip_last_error(mpCtx));
         device = false;
     }
-    for (size_t k = 0; k < K; k++) {
-        KeyFrame *pKF = vpCandidateKFs[k];
-        if (!pKF || pKF->isBad()) {          // ref: src/Tracking.cc:2598-2599
-            way[k] = -2;
-            continue;
-        }
-        uint64_t setKey = 0;
-        if (!device || !ResidentKeyFrame(pKF, &setKey)) continue;
-        way[k] = (int)cand.size();
-        const orbhip_bow_candidate c = {setKey, key_of(pKF)};
-        cand.push_back(c);
-        who.push_back(k);
-    }
+    SortCandidates(vpCandidateKFs, device, way, cand, who);
 
     // ---- the device candidates, as many to a call as the set limit leaves room for beside the frame ----
     const int nF = F.N, chunk = std::max(1, mnSetLimit - 1);
@@ -158,24 +161,12 @@ void LocalMapSearch::SearchByBoWCandidates(KeyFrame *pCurrentKF, const std::vect
     vnMatches.assign(K, 0);
     if (!pCurrentKF) return;
 
-    std::vector<int> way(K, -1);
+    std::vector<int> way;
     std::vector<orbhip_bow_candidate> cand;
     std::vector<size_t> who;
     uint64_t curSet = 0;
     const bool device = EnsureKeyFrames() && ResidentKeyFrame(pCurrentKF, &curSet);
-    for (size_t k = 0; k < K; k++) {
-        KeyFrame *pKF = vpCandidateKFs[k];
-        if (!pKF || pKF->isBad()) {
-            way[k] = -2;
-            continue;
-        }
-        uint64_t setKey = 0;
-        if (!device || !ResidentKeyFrame(pKF, &setKey)) continue;
-        way[k] = (int)cand.size();
-        const orbhip_bow_candidate c = {setKey, key_of(pKF)};
-        cand.push_back(c);
-        who.push_back(k);
-    }
+    SortCandidates(vpCandidateKFs, device, way, cand, who);
 
     const int n1 = (int)pCurrentKF->GetMapPointMatches().size(), chunk = std::max(1, mnSetLimit - 1);
     std::vector<int32_t> matches, nm;

@@ -11,7 +11,9 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::call_with_room;
 using localmapdetail::key_of;
+using localmapdetail::room_for;
 
 namespace
 {
@@ -51,7 +53,7 @@ bool LocalMapSearch::PutKeyFrameLocked(KeyFrame *pKF)
     std::vector<uint64_t> row(vpMPs.size(), 0);
     for (size_t i = 0; i < vpMPs.size(); i++) {
         MapPoint *p = vpMPs[i];
-        if (!p || !mPointOf.count(key_of(p))) continue;
+        if (!p || !Known(p)) continue;
         if (p->GetIndexInKeyFrame(pKF) != (int)i) continue;   // the vector may hold a point twice; its observation names one index
         row[i] = key_of(p);
     }
@@ -75,14 +77,28 @@ void LocalMapSearch::SetMapPoint(KeyFrame *pKF, size_t idx, MapPoint *pMP)
 void LocalMapSearch::EraseKeyFrame(KeyFrame *pKF)
 {
     std::unique_lock<std::mutex> lock(mMutex);
-    if (!mpCtx || !mbKeyFrames) return;
-    mKeyFrameOf.erase(key_of(pKF));
-    if (orbhip_map_kf_erase(mpCtx, key_of(pKF)) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::EraseKeyFrame", orbhip_last_error(mpCtx));
+    EraseKeyFrameLocked(pKF, "LocalMapSearch::EraseKeyFrame");
 }
+
+bool LocalMapSearch::EraseKeyFrameLocked(KeyFrame *pKF, const char *who)
+{
+    if (!mpCtx || !mbKeyFrames) return false;
+    mKeyFrameOf.erase(key_of(pKF));
+    if (orbhip_map_kf_erase(mpCtx, key_of(pKF)) != ORBHIP_OK) hipdetail::Fail(who, orbhip_last_error(mpCtx));
+    return true;
+}
+
+KeyFrame *LocalMapSearch::KeyFrameOf(uint64_t key) const
+{
+    const std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key);
+    return it == mKeyFrameOf.end() ? static_cast<KeyFrame *>(NULL) : it->second;
+}
+
+bool LocalMapSearch::HasRow(KeyFrame *pKF) const { return KeyFrameOf(key_of(pKF)) == pKF; }
 
 bool LocalMapSearch::CollectKeys(const std::vector<KeyFrame *> &vpKFs, std::vector<uint64_t> &kfKeys)
 {
-    // a key frame that was erased since the list was made (an empty vote keeps the last list) has no row: it adds nothing
+    // a key frame erased since the list was made (an empty vote keeps the last list) has no row: it adds nothing.  (Not HasRow: whose row is not asked)
     kfKeys.clear();
     for (size_t k = 0; k < vpKFs.size(); k++)
         if (mKeyFrameOf.count(key_of(vpKFs[k]))) kfKeys.push_back(key_of(vpKFs[k]));
@@ -98,10 +114,6 @@ void LocalMapSearch::ClearKeyFrames()
     if (orbhip_map_kf_clear(mpCtx) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::ClearKeyFrames", orbhip_last_error(mpCtx));
 }
 
-// room for a list that is usually about as long as the last one: a quarter more, and the call is made again with the exact
-// size when that was too little (the list is a function of the map, never of the room)
-static inline int room_for(size_t last, size_t most) { return (int)std::min(most, last + last / 4 + 256); }
-
 void LocalMapSearch::UpdateLocalMap(Frame &F, std::vector<KeyFrame *> &vpLocalKeyFrames, std::vector<MapPoint *> &vpLocalMapPoints,
                                     KeyFrame *&pReferenceKF)
 {
@@ -113,28 +125,23 @@ void LocalMapSearch::UpdateLocalMap(Frame &F, std::vector<KeyFrame *> &vpLocalKe
     vpLocalMapPoints.clear();
     std::vector<uint64_t> kfKeys;
     CollectKeys(vpLocalKeyFrames, kfKeys);
-    int capPts = room_for(mnLastLocal, mPointOf.size()), nlocal = 0;
+    int nlocal = 0;
     std::vector<uint64_t> local;
-    for (;;) {
-        local.resize(capPts > 0 ? capPts : 1);
-        const int rc = orbhip_map_collect(mpCtx, (int)kfKeys.size(), kfKeys.data(), local.data(), capPts, &nlocal);
-        if (rc == ORBHIP_E_CAPACITY && nlocal > capPts) {
-            capPts = nlocal;
-            continue;
-        }
-        if (rc != ORBHIP_OK) {
-            hipdetail::Fail("LocalMapSearch::UpdateLocalMap (orbhip_map_collect)", orbhip_last_error(mpCtx));
-            return;
-        }
-        break;
+    const int rc = call_with_room(room_for(mnLastLocal, mPointOf.size()), &nlocal, [&](int cap, size_t room) {
+        local.resize(room);
+        return orbhip_map_collect(mpCtx, (int)kfKeys.size(), kfKeys.data(), local.data(), cap, &nlocal);
+    });
+    if (rc != ORBHIP_OK) {
+        hipdetail::Fail("LocalMapSearch::UpdateLocalMap (orbhip_map_collect)", orbhip_last_error(mpCtx));
+        return;
     }
     mnLastLocal = nlocal;
     vpLocalMapPoints.reserve(nlocal);
-    for (int k = 0; k < nlocal; k++) {
-        std::unordered_map<uint64_t, MapPoint *>::iterator it = mPointOf.find(local[k]);
-        if (it == mPointOf.end()) continue;
-        vpLocalMapPoints.push_back(it->second);
-        it->second->mnTrackReferenceForFrame = F.mnId;
+    for (int k = 0; k < nlocal; k++) {   // an unknown key is skipped here; TrackLocalPoints fails on one
+        MapPoint *pMP = PointOf(local[k]);
+        if (!pMP) continue;
+        vpLocalMapPoints.push_back(pMP);
+        pMP->mnTrackReferenceForFrame = F.mnId;
     }
 }
 
@@ -157,20 +164,14 @@ bool LocalMapSearch::VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyF
         else
             frameKeys[i] = key_of(pMP);
     }
-    int cap = room_for(mnLastVoted, mKeyFrameOf.size()), nvoted = 0;
+    int nvoted = 0;
     std::vector<uint64_t> votedKeys;
     std::vector<int32_t> votes;
-    for (;;) {
-        votedKeys.resize(cap > 0 ? cap : 1);
-        votes.resize(cap > 0 ? cap : 1);
-        const int rc = orbhip_map_vote(mpCtx, (int)frameKeys.size(), frameKeys.data(), votedKeys.data(), votes.data(), cap, &nvoted);
-        if (rc == ORBHIP_E_CAPACITY && nvoted > cap) {
-            cap = nvoted;
-            continue;
-        }
-        if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::UpdateLocalMap (orbhip_map_vote)", orbhip_last_error(mpCtx)), false;
-        break;
-    }
+    const int rc = call_with_room(room_for(mnLastVoted, mKeyFrameOf.size()), &nvoted, [&](int cap, size_t room) {
+        votedKeys.resize(room), votes.resize(room);
+        return orbhip_map_vote(mpCtx, (int)frameKeys.size(), frameKeys.data(), votedKeys.data(), votes.data(), cap, &nvoted);
+    });
+    if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::UpdateLocalMap (orbhip_map_vote)", orbhip_last_error(mpCtx)), false;
     mnLastVoted = nvoted;
 
     if (nvoted > 0) {   // (keyframeCounter.empty(): the reference returns and keeps the lists it has)
@@ -180,10 +181,8 @@ bool LocalMapSearch::VoteAndGraph(Frame &F, std::vector<KeyFrame *> &vpLocalKeyF
         vpLocalKeyFrames.reserve(3 * nvoted);
         // ---- key frames that share points with the frame, in ascending mnId order (ref: :2445-2461) ----
         for (int k = 0; k < nvoted; k++) {
-            std::map<uint64_t, KeyFrame *>::iterator it = mKeyFrameOf.find(votedKeys[k]);
-            if (it == mKeyFrameOf.end()) continue;
-            KeyFrame *pKF = it->second;
-            if (pKF->isBad()) continue;
+            KeyFrame *pKF = KeyFrameOf(votedKeys[k]);
+            if (!pKF || pKF->isBad()) continue;
             if (votes[k] > max) {
                 max = votes[k];
                 pKFmax = pKF;
@@ -237,7 +236,7 @@ int LocalMapSearch::TrackLocalPoints(Frame &F, const std::vector<KeyFrame *> &vp
     if (nToMatch) *nToMatch = 0;
     vpLocalMapPoints.clear();
     if (!EnsureKeyFrames()) return 0;
-    if (F.mnScaleLevels < 1 || F.mnScaleLevels > 16 || (int)F.mvScaleFactors.size() < F.mnScaleLevels)
+    if (!localmapdetail::has_pyramid(F))
         return hipdetail::Fail("LocalMapSearch::TrackLocalPoints", "the frame has no scale pyramid (mnScaleLevels, mvScaleFactors)"), 0;
     const int n = F.N;
     uint64_t frameKey = 0;
@@ -252,31 +251,26 @@ int LocalMapSearch::TrackLocalPoints(Frame &F, const std::vector<KeyFrame *> &vp
     for (int i = 0; i < n; i++)   // the frame's own matches (ref: :2318-2334 stamps them with mnLastFrameSeen)
         if (F.mvpMapPoints[i] && F.mvpMapPoints[i]->mnLastFrameSeen == F.mnId) seen.push_back(key_of(F.mvpMapPoints[i]));
     const std::set<uint64_t> seenSet(seen.begin(), seen.end());
-    int cap = room_for(mnLastLocal, mPointOf.size()), nlocal = 0, ntm = 0, found = 0;
+    int nlocal = 0, ntm = 0, found = 0;
     std::vector<uint64_t> local;
     std::vector<orbhip_local_point> pts;
     std::vector<int32_t> match(n > 0 ? n : 1);
-    for (;;) {   // the result block that comes back is sized by cap, not by the list: keep cap near the list
-        local.resize(cap > 0 ? cap : 1);
-        pts.resize(cap > 0 ? cap : 1);
-        const int rc = orbhip_track_local_points(mpCtx, frameKey, (n > 0 && (int)F.mvuRight.size() == n) ? F.mvuRight.data() : NULL,
-                                                 occupied.data(), &cam, (int)kfKeys.size(), kfKeys.data(), (int)seen.size(), seen.data(),
-                                                 0.8f, local.data(), cap, &nlocal, pts.data(), &ntm, match.data(), &found);
-        if (rc == ORBHIP_E_CAPACITY && nlocal > cap) {
-            cap = nlocal;
-            continue;
-        }
-        if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::TrackLocalPoints", orbhip_last_error(mpCtx)), 0;
-        break;
-    }
+    // the result block that comes back is sized by cap, not by the list: keep cap near the list
+    const int rc = call_with_room(room_for(mnLastLocal, mPointOf.size()), &nlocal, [&](int cap, size_t room) {
+        local.resize(room), pts.resize(room);
+        return orbhip_track_local_points(mpCtx, frameKey, (n > 0 && (int)F.mvuRight.size() == n) ? F.mvuRight.data() : NULL,
+                                         occupied.data(), &cam, (int)kfKeys.size(), kfKeys.data(), (int)seen.size(), seen.data(), 0.8f,
+                                         local.data(), cap, &nlocal, pts.data(), &ntm, match.data(), &found);
+    });
+    if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::TrackLocalPoints", orbhip_last_error(mpCtx)), 0;
     mnLastLocal = nlocal;
     std::vector<uint8_t> skip(nlocal);
     vpLocalMapPoints.reserve(nlocal);
-    for (int k = 0; k < nlocal; k++) {
-        std::unordered_map<uint64_t, MapPoint *>::iterator it = mPointOf.find(local[k]);
-        if (it == mPointOf.end()) return hipdetail::Fail("LocalMapSearch::TrackLocalPoints", "a local point was never Put"), 0;
-        vpLocalMapPoints.push_back(it->second);
-        it->second->mnTrackReferenceForFrame = F.mnId;
+    for (int k = 0; k < nlocal; k++) {   // an unknown key fails here; UpdateLocalMap skips one
+        MapPoint *pMP = PointOf(local[k]);
+        if (!pMP) return hipdetail::Fail("LocalMapSearch::TrackLocalPoints", "a local point was never Put"), 0;
+        vpLocalMapPoints.push_back(pMP);
+        pMP->mnTrackReferenceForFrame = F.mnId;
         skip[k] = seenSet.count(local[k]) ? 1 : 0;   // what the device skipped: the same list, not the stamp
     }
     pts.resize(nlocal);

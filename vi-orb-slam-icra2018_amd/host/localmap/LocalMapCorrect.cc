@@ -5,7 +5,6 @@
 // point's turn in the sequence, then one Put.  A file of its own: programs that link the other LocalMap*.cc files alone do not need
 // the entry points.
 #include <algorithm>
-#include <chrono>
 #include <cstring>
 #include <map>
 #include <unordered_map>
@@ -22,15 +21,6 @@ using localmapdetail::key_of;
 
 namespace
 {
-typedef std::chrono::steady_clock Clock;
-double us_since(Clock::time_point &t0)   // and the clock starts again
-{
-    const Clock::time_point t1 = Clock::now();
-    const double us = std::chrono::duration<double, std::micro>(t1 - t0).count();
-    t0 = t1;
-    return us;
-}
-
 // g2o::Sim3::map (ref: Thirdparty/g2o/g2o/types/sim3.h:144), s*(r*xyz)+t with Eigen 3's Quaternion::_transformVector, every
 // operation rounded on its own (docs/parity.md, "CorrectLoop"; this file is built with -ffp-contract=off)
 void sim3_map(const LocalMapSearch::Sim3d &S, double v[3])
@@ -75,11 +65,8 @@ int LocalMapSearch::CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsi
 {
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx || v.empty()) return 0;
-    Clock::time_point clock = Clock::now();
+    localmapdetail::Stopwatch watch;
     const int K = (int)v.size();
-    struct ByMnId {
-        bool operator()(const std::pair<KeyFrame *, size_t> &a, const std::pair<KeyFrame *, size_t> &b) const { return a.first->mnId < b.first->mnId; }
-    };
     // the points in the sequence's order, each owned by the first key frame to reach it
     std::vector<MapPoint *> pts;
     std::vector<int> owner;
@@ -114,10 +101,8 @@ int LocalMapSearch::CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsi
     std::vector<uint8_t> refLevel;
     for (size_t i = 0; i < pts.size() && levelsOk; i++) {
         MapPoint *p = pts[i];
-        if (!mPointOf.count(key_of(p))) continue;
-        const std::map<KeyFrame *, size_t> obs = p->GetObservations();
-        std::vector<std::pair<KeyFrame *, size_t> > l(obs.begin(), obs.end());
-        std::sort(l.begin(), l.end(), ByMnId());
+        if (!Known(p)) continue;
+        const localmapdetail::ObservationList l = localmapdetail::observations_by_mnid(p);
         int ref = -1, level = 0;
         for (size_t j = 0; j < l.size(); j++)
             if (l[j].first == p->mpRefKF) ref = (int)j;
@@ -158,13 +143,11 @@ int LocalMapSearch::CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsi
 
     std::vector<uint8_t> status;
     std::vector<float> pos, nrm, mn, mx;
-    CorrectTimes().prepare += us_since(clock);
+    watch.lap(&CorrectTimes().prepare);
     if (!dev.empty()) {
         const int P = (int)dev.size();
         orbhip_refresh_params prm;
-        memset(&prm, 0, sizeof prm);
-        for (int l = 0; l < pyramid->mnScaleLevels; l++) prm.scale_factors[l] = pyramid->mvScaleFactors[l];
-        prm.nlevels = pyramid->mnScaleLevels;
+        localmapdetail::fill_refresh_params(pyramid, &prm);
         std::vector<orbhip_correct_xf> xf(K);
         for (int j = 0; j < K; j++) copy_sim3(v[j].Siw, &xf[j].Siw), copy_sim3(v[j].correctedSwi, &xf[j].corrected_Swi);
         status.resize(P), pos.resize((size_t)P * 3), nrm.resize((size_t)P * 3), mn.resize(P), mx.resize(P);
@@ -176,7 +159,7 @@ int LocalMapSearch::CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsi
         }
     }
 
-    CorrectTimes().device += us_since(clock);
+    watch.lap(&CorrectTimes().device);
     // the sequence: key frame j's points, then its SetPose.  Device results do not depend on when they are assigned; a host point
     // reads the centres as they stand at its turn
     std::vector<MapPoint *> host;
@@ -191,16 +174,12 @@ int LocalMapSearch::CorrectLoopPoints(const std::vector<LoopCorrection> &v, unsi
                 continue;
             }
             p->SetWorldPos(vec3(&pos[(size_t)d * 3]));
-            if (status[d] & 2) {
-                p->mNormalVector = vec3(&nrm[(size_t)d * 3]);
-                p->mfMinDistance = mn[d];
-                p->mfMaxDistance = mx[d];
-            }
+            if (status[d] & 2) AssignNormalDepth(p, &nrm[(size_t)d * 3], mn[d], mx[d]);
         }
         v[j].pKF->SetPose(v[j].correctedTiw);
     }
     if (!host.empty()) PutLocked(host);
-    CorrectTimes().apply += us_since(clock);
+    watch.lap(&CorrectTimes().apply);
     CorrectCounts().device += (long)(pts.size() - host.size());
     CorrectCounts().host += (long)host.size();
     return (int)pts.size();
@@ -210,7 +189,7 @@ int LocalMapSearch::ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned
 {
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx) return 0;
-    Clock::time_point clock = Clock::now();
+    localmapdetail::Stopwatch watch;
     std::unordered_set<MapPoint *> seen;
     seen.reserve(vpMPs.size());
     std::unordered_map<KeyFrame *, int> xfIndex;
@@ -244,7 +223,7 @@ int LocalMapSearch::ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned
             }
             c = it->second;
         }
-        if (!mPointOf.count(key_of(p))) {
+        if (!Known(p)) {
             host.push_back(p), hostXf.push_back(c);
             continue;
         }
@@ -258,7 +237,7 @@ int LocalMapSearch::ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned
         }
         posSet.insert(posSet.end(), g, g + 3);
     }
-    CorrectTimes().prepare += us_since(clock);
+    watch.lap(&CorrectTimes().prepare);
     if (!dev.empty()) {
         const int P = (int)dev.size();
         std::vector<uint8_t> status(P);
@@ -267,9 +246,9 @@ int LocalMapSearch::ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned
                                    pos.data()) != ORBHIP_OK) {
             hipdetail::Fail("LocalMapSearch::ApplyGlobalBA", orbhip_last_error(mpCtx));
             for (int i = 0; i < P; i++) host.push_back(dev[i]), hostXf.push_back(corr[i]);
-            CorrectTimes().device += us_since(clock);
+            watch.lap(&CorrectTimes().device);
         } else {
-            CorrectTimes().device += us_since(clock);
+            watch.lap(&CorrectTimes().device);
             for (int i = 0; i < P; i++) {
                 if (status[i] & 1) dev[i]->SetWorldPos(vec3(&pos[(size_t)i * 3])), nDevice++;
                 else host.push_back(dev[i]), hostXf.push_back(corr[i]);   // (the store holds the point as bad, the object is not)
@@ -291,7 +270,7 @@ int LocalMapSearch::ApplyGlobalBA(const std::vector<MapPoint *> &vpMPs, unsigned
         p->SetWorldPos(vec3(out));
     }
     if (!host.empty()) PutLocked(host);
-    CorrectTimes().apply += us_since(clock);
+    watch.lap(&CorrectTimes().apply);
     CorrectCounts().device += nDevice;
     CorrectCounts().host += (long)host.size();
     return (int)(nDevice + (long)host.size());

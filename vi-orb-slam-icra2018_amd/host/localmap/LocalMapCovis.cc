@@ -14,7 +14,9 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::call_with_room;
 using localmapdetail::key_of;
+using localmapdetail::room_for;
 
 namespace
 {
@@ -48,13 +50,7 @@ void LocalMapSearch::UpdateConnections(const std::vector<KeyFrame *> &vpKFs, std
         for (size_t k = 0; k < n; k++) {
             KeyFrame *pKF = vpKFs[k];
             if (!pKF) continue;
-            const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
-            bool known = true;
-            for (size_t i = 0; i < vpMPs.size() && known; i++)
-                known = !vpMPs[i] || vpMPs[i]->isBad() || mPointOf.count(key_of(vpMPs[i])) != 0;
-            if (!known) continue;
-            std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key_of(pKF));
-            if ((it == mKeyFrameOf.end() || it->second != pKF) && !PutKeyFrameLocked(pKF)) continue;
+            if (!AllKnown(pKF->GetMapPointMatches()) || !EnsureRow(pKF)) continue;   // this key frame goes the host way
             query[k] = (int)keys.size();
             keys.push_back(key_of(pKF));
         }
@@ -65,21 +61,14 @@ void LocalMapSearch::UpdateConnections(const std::vector<KeyFrame *> &vpKFs, std
     std::vector<int32_t> off(nq + 1, 0), nord(nq > 0 ? nq : 1, 0), weights, order;
     std::vector<uint64_t> nbr;
     if (nq > 0) {
-        const size_t most = (size_t)nq * mKeyFrameOf.size();
-        int cap = (int)std::min(most, (size_t)nq * (mnLastLinks + mnLastLinks / 4 + 16)), total = 0;
-        for (;;) {
-            nbr.resize(cap > 0 ? cap : 1), weights.resize(nbr.size()), order.resize(nbr.size());
-            const int rc = orbhip_map_covis(mpCtx, nq, keys.data(), kCovisTh, off.data(), nbr.data(), weights.data(), order.data(), nord.data(),
-                                            cap, &total);
-            if (rc == ORBHIP_E_CAPACITY && total > cap) {
-                cap = total;
-                continue;
-            }
-            if (rc != ORBHIP_OK) {
-                hipdetail::Fail("LocalMapSearch::UpdateConnections (orbhip_map_covis)", orbhip_last_error(mpCtx));
-                std::fill(query.begin(), query.end(), -1);   // the graph stays right: every key frame goes the host way
-            }
-            break;
+        int total = 0;
+        const int rc = call_with_room(nq * room_for(mnLastLinks, mKeyFrameOf.size(), 16), &total, [&](int cap, size_t room) {   // 16 to spare per query
+            nbr.resize(room), weights.resize(room), order.resize(room);
+            return orbhip_map_covis(mpCtx, nq, keys.data(), kCovisTh, off.data(), nbr.data(), weights.data(), order.data(), nord.data(), cap, &total);
+        });
+        if (rc != ORBHIP_OK) {
+            hipdetail::Fail("LocalMapSearch::UpdateConnections (orbhip_map_covis)", orbhip_last_error(mpCtx));
+            std::fill(query.begin(), query.end(), -1);   // the graph stays right: every key frame goes the host way
         }
         mnLastLinks = ((size_t)total + nq - 1) / nq;
     }
@@ -99,10 +88,10 @@ void LocalMapSearch::UpdateConnections(const std::vector<KeyFrame *> &vpKFs, std
             std::map<KeyFrame *, int> KFcounter;
             std::vector<KeyFrame *> seg(b - a, static_cast<KeyFrame *>(NULL));
             for (int i = a; i < b; i++) {
-                std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(nbr[i]);
-                if (it == mKeyFrameOf.end()) continue;
-                seg[i - a] = it->second;
-                KFcounter[it->second] = weights[i];
+                KeyFrame *pNbr = KeyFrameOf(nbr[i]);
+                if (!pNbr) continue;
+                seg[i - a] = pNbr;
+                KFcounter[pNbr] = weights[i];
             }
             if (!KFcounter.empty()) {   // (empty: the reference returns before it touches anything)
                 std::vector<KeyFrame *> vpOrdered;

@@ -14,7 +14,6 @@
 namespace ORB_SLAM2
 {
 
-using localmapdetail::flags_of;
 using localmapdetail::key_of;
 
 namespace
@@ -76,13 +75,8 @@ bool LocalMapSearch::CullCounts(const std::vector<KeyFrame *> &vpKFs, bool bMono
     for (size_t k = 0; k < n; k++) {
         KeyFrame *pKF = vpKFs[k];
         if (!pKF || pKF->isBad()) continue;   // (a bad key frame has no row and gets none)
-        const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
-        bool known = true;
-        for (size_t i = 0; i < vpMPs.size() && known; i++)
-            known = !vpMPs[i] || vpMPs[i]->isBad() || mPointOf.count(key_of(vpMPs[i])) != 0;
-        if (!known) continue;
-        std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key_of(pKF));
-        if ((it == mKeyFrameOf.end() || it->second != pKF) && !PutKeyFrameLocked(pKF)) return false;
+        if (!AllKnown(pKF->GetMapPointMatches())) continue;   // this key frame goes the host way
+        if (!EnsureRow(pKF)) return false;
         cand[k] = (int)keys.size();
         keys.push_back(key_of(pKF));
     }
@@ -101,8 +95,8 @@ bool LocalMapSearch::CullCounts(const std::vector<KeyFrame *> &vpKFs, bool bMono
             std::vector<int32_t> off(1, 0);
             std::vector<uint8_t> bytes;
             for (int q = 0; q < nMissing; q++) {
-                std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(missing[q]);
-                if (it == mKeyFrameOf.end() || !level_bytes(it->second, bytes)) {
+                KeyFrame *pKF = KeyFrameOf(missing[q]);
+                if (!pKF || !level_bytes(pKF, bytes)) {
                     hipdetail::Fail("LocalMapSearch::CullCounts", "a row of the table without its key frame, or an octave outside 0..15");
                     return false;
                 }
@@ -141,21 +135,15 @@ bool LocalMapSearch::CullCounts(const std::vector<KeyFrame *> &vpKFs, bool bMono
 void LocalMapSearch::KeyFrameCulled(KeyFrame *pKF, const std::vector<MapPoint *> &vpItsPoints)
 {
     std::unique_lock<std::mutex> lock(mMutex);
-    if (!mpCtx || !mbKeyFrames) return;
-    mKeyFrameOf.erase(key_of(pKF));
-    if (orbhip_map_kf_erase(mpCtx, key_of(pKF)) != ORBHIP_OK) hipdetail::Fail("LocalMapSearch::KeyFrameCulled (orbhip_map_kf_erase)", orbhip_last_error(mpCtx));
+    if (!EraseKeyFrameLocked(pKF, "LocalMapSearch::KeyFrameCulled (orbhip_map_kf_erase)")) return;
     // the points EraseObservation left with two observations or fewer turned bad: their entries in the other rows resolve no longer
     std::set<uint64_t> seen;
-    std::vector<uint64_t> keys;
-    std::vector<uint8_t> flags;
+    std::vector<MapPoint *> turnedBad;
     for (size_t i = 0; i < vpItsPoints.size(); i++) {
         MapPoint *pMP = vpItsPoints[i];
-        if (!pMP || !pMP->isBad() || !mPointOf.count(key_of(pMP)) || !seen.insert(key_of(pMP)).second) continue;
-        keys.push_back(key_of(pMP));
-        flags.push_back(flags_of(pMP));
+        if (pMP && pMP->isBad() && Known(pMP) && seen.insert(key_of(pMP)).second) turnedBad.push_back(pMP);
     }
-    if (!keys.empty() && orbhip_map_update_flags(mpCtx, (int)keys.size(), keys.data(), flags.data()) != ORBHIP_OK)
-        hipdetail::Fail("LocalMapSearch::KeyFrameCulled (orbhip_map_update_flags)", orbhip_last_error(mpCtx));
+    UpdateFlagsLocked(turnedBad.data(), turnedBad.size(), "LocalMapSearch::KeyFrameCulled (orbhip_map_update_flags)");
 }
 
 }  // namespace ORB_SLAM2

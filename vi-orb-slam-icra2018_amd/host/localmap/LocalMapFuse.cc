@@ -12,10 +12,11 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::call_with_room;
 using localmapdetail::fill_target;
-using localmapdetail::flags_of;
 using localmapdetail::has_pyramid;
 using localmapdetail::key_of;
+using localmapdetail::room_for;
 using localmapdetail::set_key_of;
 
 namespace
@@ -39,6 +40,47 @@ bool LocalMapSearch::EnsureFuseSet(KeyFrame *pKF, uint64_t *setKey)
                                  pKF->mfGridElementHeightInv, NULL);
 }
 
+void LocalMapSearch::FuseEdits::Remember(MapPoint *surv)
+{
+    if (survivors.count(surv)) return;   // (nothing has changed its descriptor since the device call, or it would be here)
+    const cv::Mat d = surv->GetDescriptor();
+    survivors[surv].assign(d.ptr(0), d.ptr(0) + 32);
+}
+
+bool LocalMapSearch::FuseEdits::ChangedSince(MapPoint *pMP) const
+{
+    const std::map<MapPoint *, std::vector<unsigned char> >::const_iterator it = survivors.find(pMP);
+    if (it == survivors.end()) return false;
+    const cv::Mat d = pMP->GetDescriptor();
+    return memcmp(d.ptr(0), it->second.data(), 32) != 0;
+}
+
+void LocalMapSearch::FuseEdits::Replace(MapPoint *dead, MapPoint *surv)
+{
+    Remember(surv);
+    const std::map<KeyFrame *, size_t> obs = dead->GetObservations();
+    dead->Replace(surv);
+    for (std::map<KeyFrame *, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it) entries.insert(std::make_pair(it->first, it->second));
+    flags.insert(dead);
+    put.insert(surv);   // its descriptor (ComputeDistinctiveDescriptors, ref: src/MapPoint.cc:227) and flags
+}
+
+bool localmapdetail::research_survivors(orbhip_ctx *ctx, const std::vector<int> &redo, const orbhip_proj_query *Q, const std::vector<MapPoint *> &vpMPs,
+                                        uint64_t setKey, const float *uRight, const float *invLevelSigma2, int nlevels, int32_t *bestIdx,
+                                        int32_t *bestDist, ResearchBuffers &b)
+{
+    const int m = (int)redo.size();
+    b.q.resize(m), b.qdesc.resize((size_t)m * 32), b.idx.resize(m), b.dist.resize(m);
+    for (int k = 0; k < m; k++) {
+        b.q[k] = Q[redo[k]];
+        const cv::Mat d = vpMPs[redo[k]]->GetDescriptor();
+        memcpy(&b.qdesc[(size_t)k * 32], d.ptr(0), 32);
+    }
+    if (orbhip_window_best_set(ctx, setKey, uRight, invLevelSigma2, nlevels, b.q.data(), b.qdesc.data(), m, b.idx.data(), b.dist.data()) != ORBHIP_OK) return false;
+    for (int k = 0; k < m; k++) bestIdx[redo[k]] = b.idx[k], bestDist[redo[k]] = b.dist[k];
+    return true;
+}
+
 // ref: src/ORBmatcher.cc:951-972 over the results of one target, in the caller's order.  An edit can change what a later point
 // sees -- a point replaced a moment ago is bad now, a feature claimed a moment ago holds a point now, a point that survived a
 // Replace is in more key frames now -- so isBad(), IsInKeyFrame() and the feature are read here, not before the search.
@@ -55,16 +97,7 @@ int LocalMapSearch::ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMP
         if (MapPoint *held = pKF->GetMapPoint(feat)) {
             if (!held->isBad()) {
                 MapPoint *dead = held->Observations() > cand->Observations() ? cand : held, *surv = dead == cand ? held : cand;
-                const std::map<KeyFrame *, size_t> obs = dead->GetObservations();
-                if (!edits.survivors.count(surv)) {   // (nothing has changed its descriptor since the device call, or it would be here)
-                    const cv::Mat d = surv->GetDescriptor();
-                    edits.survivors[surv].assign(d.ptr(0), d.ptr(0) + 32);
-                }
-                dead->Replace(surv);
-                for (std::map<KeyFrame *, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it)
-                    edits.entries.insert(std::make_pair(it->first, it->second));
-                edits.flags.insert(dead);
-                edits.put.insert(surv);           // its descriptor (ComputeDistinctiveDescriptors, ref: src/MapPoint.cc:227) and flags
+                edits.Replace(dead, surv);
             }
         } else {
             cand->AddObservation(pKF, feat);
@@ -77,50 +110,37 @@ int LocalMapSearch::ApplyFuse(KeyFrame *pKF, const std::vector<MapPoint *> &vpMP
     return fused;
 }
 
-// the store as the objects are now: survivors' descriptors and flags, the flags of every other point an edit touched
-bool LocalMapSearch::FlushFusePoints(FuseEdits &edits)
+// What FlushFuse and FlushLoop share.  The store as the objects are now: survivors' descriptors and flags, the flags of every other point
+// an edit touched.  Then the row entries an edit may have changed, for the caller to write: key frame -> (indices, point keys).  Uses up the edits.
+bool LocalMapSearch::TakeFuseEdits(FuseEdits &edits, FuseRows &rows)
 {
-    bool ok = true;
-    if (!edits.put.empty()) ok = PutLocked(std::vector<MapPoint *>(edits.put.begin(), edits.put.end())) && ok;
-    std::vector<uint64_t> keys;
-    std::vector<uint8_t> fl;
-    for (std::set<MapPoint *>::const_iterator it = edits.flags.begin(); it != edits.flags.end(); ++it) {
-        if (edits.put.count(*it) || !mPointOf.count(key_of(*it))) continue;
-        keys.push_back(key_of(*it));
-        fl.push_back(flags_of(*it));
-    }
-    if (!keys.empty() && orbhip_map_update_flags(mpCtx, (int)keys.size(), keys.data(), fl.data()) != ORBHIP_OK) {
-        hipdetail::Fail("LocalMapSearch::Fuse (orbhip_map_update_flags)", orbhip_last_error(mpCtx));
-        ok = false;
-    }
-    return ok;
-}
-
-// the row entries an edit may have changed, as the objects hold them now: key frame -> (indices, point keys)
-void LocalMapSearch::FuseRowEdits(const FuseEdits &edits, FuseRows &rows)
-{
+    bool ok = edits.put.empty() || PutLocked(std::vector<MapPoint *>(edits.put.begin(), edits.put.end()));
+    std::vector<MapPoint *> others;   // (the Put has carried the survivors' flags)
+    for (std::set<MapPoint *>::const_iterator it = edits.flags.begin(); it != edits.flags.end(); ++it)
+        if (!edits.put.count(*it) && Known(*it)) others.push_back(*it);
+    ok = UpdateFlagsLocked(others.data(), others.size(), "LocalMapSearch::Fuse (orbhip_map_update_flags)") && ok;
     for (std::set<std::pair<KeyFrame *, size_t> >::const_iterator it = edits.entries.begin(); it != edits.entries.end(); ++it) {
         KeyFrame *kf = it->first;
-        if (!mKeyFrameOf.count(key_of(kf))) continue;
+        if (!HasRow(kf)) continue;
         MapPoint *p = kf->GetMapPoint(it->second);
-        const bool named = p && mPointOf.count(key_of(p)) && p->GetIndexInKeyFrame(kf) == (int)it->second;   // PutKeyFrame's rule
+        const bool named = p && Known(p) && p->GetIndexInKeyFrame(kf) == (int)it->second;   // PutKeyFrame's rule
         rows[key_of(kf)].first.push_back((int32_t)it->second);
         rows[key_of(kf)].second.push_back(named ? key_of(p) : 0);
     }
+    edits.put.clear(), edits.flags.clear(), edits.entries.clear();
+    return ok;
 }
 
 // the store and the table as the objects are now
 bool LocalMapSearch::FlushFuse(FuseEdits &edits)
 {
-    bool ok = FlushFusePoints(edits);
     FuseRows rows;
-    FuseRowEdits(edits, rows);
+    bool ok = TakeFuseEdits(edits, rows);
     for (FuseRows::const_iterator it = rows.begin(); it != rows.end(); ++it)
         if (orbhip_map_kf_set(mpCtx, it->first, (int)it->second.first.size(), it->second.first.data(), it->second.second.data()) != ORBHIP_OK) {
             hipdetail::Fail("LocalMapSearch::Fuse (orbhip_map_kf_set)", orbhip_last_error(mpCtx));
             ok = false;
         }
-    edits.put.clear(), edits.flags.clear(), edits.entries.clear();
     return ok;
 }
 
@@ -133,7 +153,7 @@ std::vector<int> LocalMapSearch::FuseInTargets(KeyFrame *pKF, const std::vector<
     const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();     // ref: src/LocalMapping.cc:2551 (one copy for all targets)
     const int n = (int)vpMPs.size();
     if (n == 0) return nFused;
-    if (!mKeyFrameOf.count(key_of(pKF)) && !PutKeyFrameLocked(pKF)) return nFused;
+    if (!EnsureRow(pKF)) return nFused;
     for (int k = 0; k < K; k++)
         if (!has_pyramid(vpTargetKFs[k]))
             return hipdetail::Fail("LocalMapSearch::FuseInTargets", "a target has no scale pyramid (mnScaleLevels, mvScaleFactors, mvInvLevelSigma2)"), nFused;
@@ -142,17 +162,17 @@ std::vector<int> LocalMapSearch::FuseInTargets(KeyFrame *pKF, const std::vector<
     if (K > FUSE_CHUNK) {
         snapshot.assign(n, 0);
         for (int i = 0; i < n; i++)
-            if (vpMPs[i] && mPointOf.count(key_of(vpMPs[i])) && vpMPs[i]->GetIndexInKeyFrame(pKF) == i) snapshot[i] = key_of(vpMPs[i]);
+            if (vpMPs[i] && Known(vpMPs[i]) && vpMPs[i]->GetIndexInKeyFrame(pKF) == i) snapshot[i] = key_of(vpMPs[i]);
     }
     FuseEdits edits;
     bool snapshotPut = false;
     std::vector<orbhip_fuse_target> targets;
     std::vector<uint8_t> skip;
     std::vector<float> uRight;
-    std::vector<orbhip_proj_query> queries, q;
-    std::vector<int32_t> bestIdx, bestDist, nActive, rbi, rbd;
-    std::vector<uint8_t> qdesc;
+    std::vector<orbhip_proj_query> queries;
+    std::vector<int32_t> bestIdx, bestDist, nActive;
     std::vector<int> redo;
+    localmapdetail::ResearchBuffers again;
     for (int start = 0; start < K; start += FUSE_CHUNK) {
         const int cnt = std::min(FUSE_CHUNK, K - start);
         uint64_t rowKey = key_of(pKF);
@@ -193,29 +213,15 @@ std::vector<int> LocalMapSearch::FuseInTargets(KeyFrame *pKF, const std::vector<
             KeyFrame *pKFi = vpTargetKFs[start + j];
             const orbhip_proj_query *Q = &queries[(size_t)j * n];
             // points whose descriptor changed since the call (they survived a Replace in an earlier target): their windows are
-            // what they were, their best feature may not be
+            // what they were, their best feature may not be.  (SearchAndFuse asks more of a point, and searches without uRight and sigmas)
             redo.clear();
-            for (int i = 0; i < n && !edits.survivors.empty(); i++) {
-                if (!(Q[i].flags & ORBHIP_Q_ACTIVE) || !vpMPs[i]) continue;
-                std::map<MapPoint *, std::vector<unsigned char> >::const_iterator it = edits.survivors.find(vpMPs[i]);
-                if (it == edits.survivors.end()) continue;
-                const cv::Mat d = vpMPs[i]->GetDescriptor();
-                if (memcmp(d.ptr(0), it->second.data(), 32) != 0) redo.push_back(i);
-            }
-            if (!redo.empty()) {
-                const int m = (int)redo.size();
-                q.resize(m), qdesc.resize((size_t)m * 32), rbi.resize(m), rbd.resize(m);
-                for (int k = 0; k < m; k++) {
-                    q[k] = Q[redo[k]];
-                    const cv::Mat d = vpMPs[redo[k]]->GetDescriptor();
-                    memcpy(&qdesc[(size_t)k * 32], d.ptr(0), 32);
-                }
-                if (orbhip_window_best_set(mpCtx, targets[j].set_key, anyStereo ? &uRight[urAt[j]] : NULL, targets[j].inv_level_sigma2,
-                                           pKFi->mnScaleLevels, q.data(), qdesc.data(), m, rbi.data(), rbd.data()) != ORBHIP_OK)
-                    return hipdetail::Fail("LocalMapSearch::FuseInTargets (orbhip_window_best_set)", orbhip_last_error(mpCtx)), nFused;
-                for (int k = 0; k < m; k++) bestIdx[(size_t)j * n + redo[k]] = rbi[k], bestDist[(size_t)j * n + redo[k]] = rbd[k];
-            }
-            nFused[start + j] = ApplyFuse(pKFi, vpMPs, &bestIdx[(size_t)j * n], &bestDist[(size_t)j * n], edits);
+            for (int i = 0; i < n && !edits.survivors.empty(); i++)
+                if ((Q[i].flags & ORBHIP_Q_ACTIVE) && vpMPs[i] && edits.ChangedSince(vpMPs[i])) redo.push_back(i);
+            int32_t *bi = &bestIdx[(size_t)j * n], *bd = &bestDist[(size_t)j * n];
+            if (!redo.empty() && !localmapdetail::research_survivors(mpCtx, redo, Q, vpMPs, targets[j].set_key, anyStereo ? &uRight[urAt[j]] : NULL,
+                                                                     targets[j].inv_level_sigma2, pKFi->mnScaleLevels, bi, bd, again))
+                return hipdetail::Fail("LocalMapSearch::FuseInTargets (orbhip_window_best_set)", orbhip_last_error(mpCtx)), nFused;
+            nFused[start + j] = ApplyFuse(pKFi, vpMPs, bi, bd, edits);
         }
     }
     FlushFuse(edits);
@@ -229,36 +235,27 @@ int LocalMapSearch::FuseCandidates(KeyFrame *pKF, const std::vector<KeyFrame *> 
     if (vpTargetKFs.empty() || !EnsureKeyFrames()) return 0;
     if (!has_pyramid(pKF))
         return hipdetail::Fail("LocalMapSearch::FuseCandidates", "the key frame has no scale pyramid (mnScaleLevels, mvScaleFactors, mvInvLevelSigma2)"), 0;
-    if (!mKeyFrameOf.count(key_of(pKF)) && !PutKeyFrameLocked(pKF)) return 0;
+    if (!EnsureRow(pKF)) return 0;
     for (size_t k = 0; k < vpTargetKFs.size(); k++)
-        if (!mKeyFrameOf.count(key_of(vpTargetKFs[k])) && !PutKeyFrameLocked(vpTargetKFs[k])) return 0;
+        if (!EnsureRow(vpTargetKFs[k])) return 0;
     std::vector<uint64_t> kfKeys;
     CollectKeys(vpTargetKFs, kfKeys);
     uint64_t setKey = 0;
     if (!EnsureFuseSet(pKF, &setKey)) return hipdetail::Fail("LocalMapSearch::FuseCandidates (key frame set)", orbhip_last_error(mpCtx)), 0;
     orbhip_fuse_target target;
     fill_target(pKF, setKey, th, &target);
-    int cap = (int)std::min(mPointOf.size(), mnLastCandidates + mnLastCandidates / 4 + 256), ncand = 0, nActive = 0;
+    int ncand = 0, nActive = 0;
     std::vector<uint64_t> keys;
     std::vector<int32_t> bestIdx, bestDist;
-    for (;;) {   // the list is a function of the map, never of the room: too little room, and the call is made again with enough
-        keys.resize(cap > 0 ? cap : 1), bestIdx.resize(cap > 0 ? cap : 1), bestDist.resize(cap > 0 ? cap : 1);
-        const int rc = orbhip_fuse_collect(mpCtx, &target, key_of(pKF), (int)kfKeys.size(), kfKeys.data(),
-                                           is_stereo(pKF) ? pKF->mvuRight.data() : NULL, keys.data(), cap, &ncand, NULL, bestIdx.data(),
-                                           bestDist.data(), &nActive);
-        if (rc == ORBHIP_E_CAPACITY && ncand > cap) {
-            cap = ncand;
-            continue;
-        }
-        if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::FuseCandidates", orbhip_last_error(mpCtx)), 0;
-        break;
-    }
+    const int rc = call_with_room(room_for(mnLastCandidates, mPointOf.size()), &ncand, [&](int cap, size_t room) {
+        keys.resize(room), bestIdx.resize(room), bestDist.resize(room);
+        return orbhip_fuse_collect(mpCtx, &target, key_of(pKF), (int)kfKeys.size(), kfKeys.data(), is_stereo(pKF) ? pKF->mvuRight.data() : NULL,
+                                   keys.data(), cap, &ncand, NULL, bestIdx.data(), bestDist.data(), &nActive);
+    });
+    if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::FuseCandidates", orbhip_last_error(mpCtx)), 0;
     mnLastCandidates = ncand;
-    std::vector<MapPoint *> vpCandidates(ncand, static_cast<MapPoint *>(NULL));   // ref: src/LocalMapping.cc:2563-2580, element for element
-    for (int k = 0; k < ncand; k++) {
-        std::unordered_map<uint64_t, MapPoint *>::iterator it = mPointOf.find(keys[k]);
-        if (it != mPointOf.end()) vpCandidates[k] = it->second;
-    }
+    std::vector<MapPoint *> vpCandidates;
+    PointsOf(keys.data(), ncand, vpCandidates);   // ref: src/LocalMapping.cc:2563-2580, element for element
     FuseEdits edits;
     const int fused = ApplyFuse(pKF, vpCandidates, bestIdx.data(), bestDist.data(), edits);
     FlushFuse(edits);

@@ -5,7 +5,6 @@
 // state brought up to date once per device call, the table with one orbhip_map_kf_set_batch.  A file of its own: programs that
 // link the other LocalMap*.cc files alone need none of the three entry points.
 #include <algorithm>
-#include <chrono>
 
 #include "LocalMapDetail.h"
 #include "../MatcherDetail.h"
@@ -14,23 +13,16 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::call_with_room;
 using localmapdetail::fill_target;
 using localmapdetail::has_pyramid;
 using localmapdetail::key_of;
+using localmapdetail::room_for;
 
 namespace
 {
 const int LOOP_CHUNK = 64;   // targets per device call, as FuseInTargets
 const int TH_LOW = 50;       // ORBmatcher::TH_LOW
-
-typedef std::chrono::steady_clock Clock;
-// adds the time since *t0 to `sum` and restarts the clock
-void lap(Clock::time_point *t0, double *sum)
-{
-    const Clock::time_point t1 = Clock::now();
-    *sum += std::chrono::duration<double, std::micro>(t1 - *t0).count();
-    *t0 = t1;
-}
 
 // the target with Rcw, tcw, Ow of the similarity (ref: src/ORBmatcher.cc:299-303, :986-990)
 void fill_sim3_target(KeyFrame *pKF, uint64_t setKey, const cv::Mat &Scw, float th, orbhip_fuse_target *out)
@@ -45,9 +37,8 @@ void fill_sim3_target(KeyFrame *pKF, uint64_t setKey, const cv::Mat &Scw, float 
 
 bool LocalMapSearch::FlushLoop(FuseEdits &edits)
 {
-    bool ok = FlushFusePoints(edits);
     FuseRows rows;
-    FuseRowEdits(edits, rows);
+    bool ok = TakeFuseEdits(edits, rows);
     std::vector<uint64_t> kf, pt;
     std::vector<int32_t> idx;
     for (FuseRows::const_iterator it = rows.begin(); it != rows.end(); ++it) {
@@ -59,7 +50,6 @@ bool LocalMapSearch::FlushLoop(FuseEdits &edits)
         hipdetail::Fail("LocalMapSearch::SearchAndFuse (orbhip_map_kf_set_batch)", orbhip_last_error(mpCtx));
         ok = false;
     }
-    edits.put.clear(), edits.flags.clear(), edits.entries.clear();
     return ok;
 }
 
@@ -75,7 +65,7 @@ int LocalMapSearch::SearchLoopPoints(KeyFrame *pCurrentKF, const cv::Mat &Scw, c
     if ((int)vpCurrentMatchedPoints.size() != n)
         return hipdetail::Fail("LocalMapSearch::SearchLoopPoints", "vpCurrentMatchedPoints is not as long as the key frame's features"), 0;
     for (size_t k = 0; k < vpLoopConnectedKFs.size(); k++)
-        if (!mKeyFrameOf.count(key_of(vpLoopConnectedKFs[k])) && !PutKeyFrameLocked(vpLoopConnectedKFs[k])) return 0;
+        if (!EnsureRow(vpLoopConnectedKFs[k])) return 0;
     std::vector<uint64_t> kfKeys;
     CollectKeys(vpLoopConnectedKFs, kfKeys);
     if (n == 0 || kfKeys.empty()) return 0;
@@ -86,26 +76,17 @@ int LocalMapSearch::SearchLoopPoints(KeyFrame *pCurrentKF, const cv::Mat &Scw, c
     std::vector<uint64_t> matched(n, 0);                                            // vpMatched as keys (ref: src/ORBmatcher.cc:306-307, :375)
     for (int i = 0; i < n; i++)
         if (vpCurrentMatchedPoints[i]) matched[i] = key_of(vpCurrentMatchedPoints[i]);
-    int cap = (int)std::min(mPointOf.size(), mnLastLoopPoints + mnLastLoopPoints / 4 + 256), npoints = 0, nActive = 0, nmatches = 0;
+    int npoints = 0, nActive = 0, nmatches = 0;
     std::vector<uint64_t> keys;
     std::vector<int32_t> match(n);
-    for (;;) {   // the list is a function of the map, never of the room: too little room, and the call is made again with enough
-        keys.resize(cap > 0 ? cap : 1);
-        const int rc = orbhip_search_loop_points(mpCtx, &target, (int)kfKeys.size(), kfKeys.data(), matched.data(), TH_LOW, keys.data(), cap,
-                                                 &npoints, NULL, &nActive, match.data(), &nmatches);
-        if (rc == ORBHIP_E_CAPACITY && npoints > cap) {
-            cap = npoints;
-            continue;
-        }
-        if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::SearchLoopPoints", orbhip_last_error(mpCtx)), 0;
-        break;
-    }
+    const int rc = call_with_room(room_for(mnLastLoopPoints, mPointOf.size()), &npoints, [&](int cap, size_t room) {
+        keys.resize(room);
+        return orbhip_search_loop_points(mpCtx, &target, (int)kfKeys.size(), kfKeys.data(), matched.data(), TH_LOW, keys.data(), cap, &npoints,
+                                         NULL, &nActive, match.data(), &nmatches);
+    });
+    if (rc != ORBHIP_OK) return hipdetail::Fail("LocalMapSearch::SearchLoopPoints", orbhip_last_error(mpCtx)), 0;
     mnLastLoopPoints = npoints;
-    vpLoopMapPoints.assign(npoints, static_cast<MapPoint *>(NULL));                 // ref: src/LoopClosing.cc:408-424, element for element
-    for (int k = 0; k < npoints; k++) {
-        std::unordered_map<uint64_t, MapPoint *>::iterator it = mPointOf.find(keys[k]);
-        if (it != mPointOf.end()) vpLoopMapPoints[k] = it->second;
-    }
+    PointsOf(keys.data(), npoints, vpLoopMapPoints);                                // ref: src/LoopClosing.cc:408-424, element for element
     for (int i = 0; i < n; i++)
         if (match[i] >= 0 && match[i] < npoints) vpCurrentMatchedPoints[i] = vpLoopMapPoints[match[i]];   // ref: src/ORBmatcher.cc:396
     return nmatches;
@@ -118,27 +99,27 @@ void LocalMapSearch::SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::M
     const int K = (int)vCorrectedPoses.size(), n = (int)vpLoopMapPoints.size();
     if (K == 0 || n == 0 || !EnsureKeyFrames()) return;
     LoopPhases &ph = Phases();
-    Clock::time_point t0 = Clock::now();
+    localmapdetail::Stopwatch watch;
     for (int k = 0; k < K; k++) {
         KeyFrame *pKF = vCorrectedPoses[k].first;
         if (!has_pyramid(pKF))
             return (void)hipdetail::Fail("LocalMapSearch::SearchAndFuse", "a key frame has no scale pyramid (mnScaleLevels, mvScaleFactors, mvInvLevelSigma2)");
-        if (!mKeyFrameOf.count(key_of(pKF)) && !PutKeyFrameLocked(pKF)) return;
+        if (!EnsureRow(pKF)) return;
     }
     std::vector<uint64_t> pointKeys(n, 0);           // a point that was never Put, or that the list names a second time, takes no part
     {
         std::set<MapPoint *> seen;
         for (int i = 0; i < n; i++)
-            if (vpLoopMapPoints[i] && mPointOf.count(key_of(vpLoopMapPoints[i])) && seen.insert(vpLoopMapPoints[i]).second)
+            if (vpLoopMapPoints[i] && Known(vpLoopMapPoints[i]) && seen.insert(vpLoopMapPoints[i]).second)
                 pointKeys[i] = key_of(vpLoopMapPoints[i]);
     }
     FuseEdits edits;
     std::vector<orbhip_fuse_target> targets;
     std::vector<uint64_t> rowKeys;
-    std::vector<orbhip_proj_query> queries, q;
-    std::vector<int32_t> bestIdx, bestDist, nActive, rbi, rbd;
-    std::vector<uint8_t> qdesc;
+    std::vector<orbhip_proj_query> queries;
+    std::vector<int32_t> bestIdx, bestDist, nActive;
     std::vector<int> redo;
+    localmapdetail::ResearchBuffers again;
     std::vector<MapPoint *> vpReplacePoints;
     for (int start = 0; start < K; start += LOOP_CHUNK) {
         const int cnt = std::min(LOOP_CHUNK, K - start);
@@ -152,11 +133,11 @@ void LocalMapSearch::SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::M
         }
         const size_t total = (size_t)cnt * n;
         queries.resize(total), bestIdx.resize(total), bestDist.resize(total), nActive.resize(cnt);
-        lap(&t0, &ph.prepare);
+        watch.lap(&ph.prepare);
         if (orbhip_fuse_sim3(mpCtx, targets.data(), rowKeys.data(), cnt, pointKeys.data(), n, queries.data(), bestIdx.data(), bestDist.data(),
                              nActive.data()) != ORBHIP_OK)
             return (void)hipdetail::Fail("LocalMapSearch::SearchAndFuse", orbhip_last_error(mpCtx));
-        lap(&t0, &ph.device);
+        watch.lap(&ph.device);
         for (int j = 0; j < cnt; j++) {
             KeyFrame *pKF = vCorrectedPoses[start + j].first;
             const orbhip_proj_query *Q = &queries[(size_t)j * n];
@@ -164,29 +145,16 @@ void LocalMapSearch::SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::M
             const std::set<MapPoint *> spAlreadyFound = pKF->GetMapPoints();          // ref: src/ORBmatcher.cc:993, as it is NOW
             const int nFeat = (int)pKF->GetMapPointMatches().size();
             // loop points whose descriptor changed since the call (they survived a Replace in an earlier target): their windows
-            // are what they were, their best feature may not be
+            // are what they were, their best feature may not be.  (FuseInTargets asks less of a point, and searches with uRight and sigmas)
             redo.clear();
             for (int i = 0; i < n && !edits.survivors.empty() && ResearchChangedSurvivors(); i++) {
                 MapPoint *pMP = vpLoopMapPoints[i];
                 if (!(Q[i].flags & ORBHIP_Q_ACTIVE) || !pointKeys[i] || pMP->isBad() || spAlreadyFound.count(pMP)) continue;
-                std::map<MapPoint *, std::vector<unsigned char> >::const_iterator it = edits.survivors.find(pMP);
-                if (it == edits.survivors.end()) continue;
-                const cv::Mat d = pMP->GetDescriptor();
-                if (memcmp(d.ptr(0), it->second.data(), 32) != 0) redo.push_back(i);
+                if (edits.ChangedSince(pMP)) redo.push_back(i);
             }
-            if (!redo.empty()) {
-                const int m = (int)redo.size();
-                q.resize(m), qdesc.resize((size_t)m * 32), rbi.resize(m), rbd.resize(m);
-                for (int k = 0; k < m; k++) {
-                    q[k] = Q[redo[k]];
-                    const cv::Mat d = vpLoopMapPoints[redo[k]]->GetDescriptor();
-                    memcpy(&qdesc[(size_t)k * 32], d.ptr(0), 32);
-                }
-                if (orbhip_window_best_set(mpCtx, targets[j].set_key, NULL, NULL, 0, q.data(), qdesc.data(), m, rbi.data(), rbd.data()) != ORBHIP_OK)
-                    return (void)hipdetail::Fail("LocalMapSearch::SearchAndFuse (orbhip_window_best_set)", orbhip_last_error(mpCtx));
-                for (int k = 0; k < m; k++) bi[redo[k]] = rbi[k], bd[redo[k]] = rbd[k];
-            }
-            lap(&t0, &ph.research);
+            if (!redo.empty() && !localmapdetail::research_survivors(mpCtx, redo, Q, vpLoopMapPoints, targets[j].set_key, NULL, NULL, 0, bi, bd, again))
+                return (void)hipdetail::Fail("LocalMapSearch::SearchAndFuse (orbhip_window_best_set)", orbhip_last_error(mpCtx));
+            watch.lap(&ph.research);
             // ref: src/ORBmatcher.cc:1081-1096 over the results, in list order
             vpReplacePoints.assign(n, static_cast<MapPoint *>(NULL));                 // ref: src/LoopClosing.cc:658
             for (int i = 0; i < n; i++) {
@@ -208,22 +176,12 @@ void LocalMapSearch::SearchAndFuse(const std::vector<std::pair<KeyFrame *, cv::M
             // ref: src/LoopClosing.cc:663-671
             for (int i = 0; i < n; i++) {
                 MapPoint *pRep = vpReplacePoints[i], *pMP = vpLoopMapPoints[i];
-                if (!pRep) continue;
-                if (!edits.survivors.count(pMP)) {       // (nothing has changed its descriptor since the device call, or it would be here)
-                    const cv::Mat d = pMP->GetDescriptor();
-                    edits.survivors[pMP].assign(d.ptr(0), d.ptr(0) + 32);
-                }
-                const std::map<KeyFrame *, size_t> obs = pRep->GetObservations();
-                pRep->Replace(pMP);
-                for (std::map<KeyFrame *, size_t>::const_iterator it = obs.begin(); it != obs.end(); ++it)
-                    edits.entries.insert(std::make_pair(it->first, it->second));
-                edits.flags.insert(pRep);
-                edits.put.insert(pMP);                   // its descriptor (ComputeDistinctiveDescriptors, ref: src/MapPoint.cc:227) and flags
+                if (pRep) edits.Replace(pRep, pMP);
             }
-            lap(&t0, &ph.apply);
+            watch.lap(&ph.apply);
         }
         const bool flushed = FlushLoop(edits);           // once per device call
-        lap(&t0, &ph.resident);
+        watch.lap(&ph.resident);
         if (!flushed) return;
         edits.survivors.clear();                         // the store has their descriptors now
     }

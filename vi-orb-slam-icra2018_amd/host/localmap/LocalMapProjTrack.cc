@@ -12,12 +12,11 @@
 namespace ORB_SLAM2
 {
 
+using localmapdetail::has_pyramid;
 using localmapdetail::key_of;
 
 namespace
 {
-bool has_pyramid(const Frame &F) { return F.mnScaleLevels >= 1 && F.mnScaleLevels <= 16 && (int)F.mvScaleFactors.size() >= F.mnScaleLevels; }
-
 // match[] of the window search -> Cur.mvpMapPoints the way the reference's loops write it (ref: :1452, :1489, :1579, :1617)
 void write_matches(Frame &Cur, const std::vector<int32_t> &match, const std::vector<MapPoint *> &source)
 {
@@ -58,7 +57,7 @@ int LocalMapSearch::SearchLastFrame(Frame &Cur, const Frame &Last, float th, boo
         MapPoint *p = Last.mvpMapPoints[i];
         if (!p || Last.mvbOutlier[i]) continue;                   // ref: :1370-1372
         keys[i] = key_of(p);
-        if (!mPointOf.count(keys[i]) && std::find(fresh.begin(), fresh.end(), p) == fresh.end()) fresh.push_back(p);
+        if (!Known(p) && std::find(fresh.begin(), fresh.end(), p) == fresh.end()) fresh.push_back(p);
     }
     if (!PutLocked(fresh)) return 0;
 
@@ -85,12 +84,12 @@ int LocalMapSearch::SearchKeyFramePoints(Frame &Cur, KeyFrame *pKF, const std::s
     const int n = Cur.N, nq = (int)vpMPs.size();
     if (n == 0 || nq == 0) return 0;
     if (!has_pyramid(Cur)) return hipdetail::Fail("LocalMapSearch::SearchKeyFramePoints", "the frame has no scale pyramid (mnScaleLevels, mvScaleFactors)"), 0;
-    if (!mKeyFrameOf.count(key_of(pKF)) && !PutKeyFrameLocked(pKF)) return 0;
+    if (!EnsureRow(pKF)) return 0;
 
     uint64_t curKey = 0;
     if (!localmapdetail::put_frame(mpCtx, Cur, &curKey))
         return hipdetail::Fail("LocalMapSearch::SearchKeyFramePoints (orbhip_set_put)", orbhip_last_error(mpCtx)), 0;
-    const uint64_t kfSetKey = localmapdetail::set_key_of(pKF);
+    const uint64_t kfSetKey = localmapdetail::set_key_of(pKF);   // (not EnsureFuseSet: that raises the set limit on first use)
     if (!hipdetail::ensure_set(mpCtx, kfSetKey, *pKF, pKF->mvKeysUn, pKF->mnMinX, pKF->mnMinY, pKF->mfGridElementWidthInv,
                                pKF->mfGridElementHeightInv, NULL))
         return hipdetail::Fail("LocalMapSearch::SearchKeyFramePoints (key frame set)", orbhip_last_error(mpCtx)), 0;

@@ -28,10 +28,7 @@ int LocalMapSearch::RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDe
 {
     std::unique_lock<std::mutex> lock(mMutex);
     if (!mpCtx || (!bDescriptors && !bNormals)) return 0;
-    typedef std::vector<std::pair<KeyFrame *, size_t> > List;   // a point's observations in ascending KeyFrame::mnId
-    struct ByMnId {
-        bool operator()(const std::pair<KeyFrame *, size_t> &a, const std::pair<KeyFrame *, size_t> &b) const { return a.first->mnId < b.first->mnId; }
-    };
+    typedef localmapdetail::ObservationList List;   // a point's observations in ascending KeyFrame::mnId
     std::vector<MapPoint *> pts;
     std::vector<List> lists;
     std::set<MapPoint *> seen;
@@ -39,10 +36,8 @@ int LocalMapSearch::RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDe
     for (size_t i = 0; i < vpMPs.size(); i++) {
         MapPoint *p = vpMPs[i];
         if (!p || p->isBad() || !seen.insert(p).second) continue;
-        const std::map<KeyFrame *, size_t> obs = p->GetObservations();
-        if (obs.empty()) continue;                               // (both methods return at once)
-        List l(obs.begin(), obs.end());
-        std::sort(l.begin(), l.end(), ByMnId());
+        const List l = localmapdetail::observations_by_mnid(p);
+        if (l.empty()) continue;                                 // (both methods return at once)
         for (size_t j = 0; j < l.size(); j++) observers[l[j].first->mnId] = l[j].first;
         pts.push_back(p);
         lists.push_back(l);
@@ -75,7 +70,7 @@ int LocalMapSearch::RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDe
     for (size_t i = 0; i < pts.size(); i++) {
         MapPoint *p = pts[i];
         const List &l = lists[i];
-        bool ok = mPointOf.count(key_of(p)) != 0;
+        bool ok = Known(p);
         int ref = 0;
         for (size_t j = 0; j < l.size() && ok; j++) {
             ok = kfIndex.count(l[j].first) != 0 && (int)l[j].second < l[j].first->N;
@@ -97,9 +92,7 @@ int LocalMapSearch::RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDe
     if (!dev.empty()) {
         const int P = (int)dev.size();
         orbhip_refresh_params prm;
-        memset(&prm, 0, sizeof prm);
-        for (int l = 0; l < pyramid->mnScaleLevels; l++) prm.scale_factors[l] = pyramid->mvScaleFactors[l];
-        prm.nlevels = pyramid->mnScaleLevels;
+        localmapdetail::fill_refresh_params(pyramid, &prm);
         prm.what = (bDescriptors ? ORBHIP_REFRESH_DESC : 0) | (bNormals ? ORBHIP_REFRESH_NORMAL : 0);
         std::vector<uint8_t> status(P), desc((size_t)P * 32);
         std::vector<float> nrm((size_t)P * 3), mn(P), mx(P);
@@ -115,13 +108,7 @@ int LocalMapSearch::RefreshPoints(const std::vector<MapPoint *> &vpMPs, bool bDe
                     memcpy(d.ptr(0), &desc[(size_t)i * 32], 32);
                     p->mDescriptor = d;
                 }
-                if (status[i] & ORBHIP_REFRESH_NORMAL) {
-                    cv::Mat n(3, 1, CV_32F);
-                    for (int c = 0; c < 3; c++) n.at<float>(c, 0) = nrm[(size_t)i * 3 + c];
-                    p->mNormalVector = n;
-                    p->mfMinDistance = mn[i];
-                    p->mfMaxDistance = mx[i];
-                }
+                if (status[i] & ORBHIP_REFRESH_NORMAL) AssignNormalDepth(p, &nrm[(size_t)i * 3], mn[i], mx[i]);
             }
             touched += P;
             RefreshCounts().device += P;

@@ -29,12 +29,9 @@ int LocalMapSearch::SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<Map
     std::vector<MapPoint *> points[2];
     for (int s = 0; s < 2; s++) {
         // can the table speak for the key frame?  It has a row, and every non-NULL, non-bad point is known to the store
-        std::map<uint64_t, KeyFrame *>::const_iterator it = mKeyFrameOf.find(key_of(kf[s]));
-        if (it == mKeyFrameOf.end() || it->second != kf[s] || !has_pyramid(kf[s])) return -1;
+        if (!HasRow(kf[s]) || !has_pyramid(kf[s])) return -1;   // (tests, does not put: the caller's way out is the host matcher)
         points[s] = kf[s]->GetMapPointMatches();
-        if (points[s].empty() || (int)points[s].size() != kf[s]->mDescriptors.rows) return -1;
-        for (size_t i = 0; i < points[s].size(); i++)
-            if (points[s][i] && !points[s][i]->isBad() && !mPointOf.count(key_of(points[s][i]))) return -1;
+        if (points[s].empty() || (int)points[s].size() != kf[s]->mDescriptors.rows || !AllKnown(points[s])) return -1;
     }
     const int N1 = (int)points[0].size(), N2 = (int)points[1].size();
     if ((int)vpMatches12.size() != N1) return -1;
